@@ -47,8 +47,19 @@ GPU.  Each rank binds GPU LOCAL_RANK and marches its own B scenarios (weak
 scaling, no collective in the data path; the only RCCL calls are the timing
 barrier and the max over ranks).
 
+A plain run does only what the line's headline figure needs: set-up, warm-up,
+the K timed steps, the result line.  --full adds everything else the benchmark
+measures or checks, each in runs of its own after the timed steps: the CPU
+baselines and the parity record against the C oracle (cpu_baseline, parity),
+the host-array rate (pcie_inclusive), --overlap-streams, the whole-grid run
+of trade_double.  --dump-outputs DIR writes what the last timed step computed
+(the arrays its caller receives) as DIR/<name>.npy, float64; the inputs are
+the same on every run with the same arguments, so two builds compare output
+for output.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
-                       [--workload NAME] [--dry-run]
+                       [--workload NAME] [--full] [--dump-outputs DIR]
+                       [--dry-run]
 """
 from __future__ import annotations
 
@@ -89,6 +100,44 @@ PARITY_TOL = 1e-10
 
 
 WARM_SECONDS = 1.0
+# --dump-outputs: bytes written per run at most, and the seed of the row sample
+DUMP_CAP_BYTES = 48 << 20
+DUMP_SEED = 20250728
+
+
+def dump_outputs(directory: str, arrays: dict, suffix: str = "") -> dict:
+    """Write `arrays` (name -> what the last timed step returned) as
+    DIR/<name><suffix>.npy in float64 and return the record of the line.
+    Non-numeric entries are left out.  If everything together exceeds
+    DUMP_CAP_BYTES, every array with more than one row keeps a sample of its
+    rows (axis 0) drawn once from DUMP_SEED -- the same rows on every run of
+    the same shapes -- whose indices go to <name>_rows<suffix>.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        try:
+            a = np.asarray(a)
+            if a.dtype.kind not in "fiub":
+                continue
+            arrs[name] = np.ascontiguousarray(a, dtype=np.float64)
+        except (TypeError, ValueError):
+            continue
+    total = sum(a.nbytes for a in arrs.values())
+    rec = {}
+    for name, a in arrs.items():
+        rows = None
+        if total > DUMP_CAP_BYTES and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_CAP_BYTES / total * 0.98))
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], keep,
+                                                                   replace=False))
+            a = a[rows]
+            np.save(os.path.join(directory, f"{name}_rows{suffix}.npy"),
+                    rows.astype(np.float64))
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), a)
+        rec[name + suffix] = {"shape": list(a.shape), "dtype": "float64",
+                              "sampled_rows": None if rows is None else int(len(rows))}
+    return rec
 
 
 def warm_up(step, args, sync=None) -> int:
@@ -117,7 +166,7 @@ def warm_up(step, args, sync=None) -> int:
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=None,
                     help="untimed warm-up steps (default: at least 2, continued until "
                          "WARM_SECONDS of them have run: the clock ramps over the first ~1 s "
@@ -139,20 +188,36 @@ def parse(argv=None):
                          "(include/fdcn_diag.h)")
     ap.add_argument("--n-space", type=int, default=0, help="0: workload default")
     ap.add_argument("--n-time", type=int, default=0, help="0: workload default")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not "
+                         "need: the CPU baselines and the parity record against the C oracle, "
+                         "the host-array (pcie_inclusive) launches, --overlap-streams, the "
+                         "whole-grid run of trade_double")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; "
+                         f"above {DUMP_CAP_BYTES >> 20} MiB in all, a fixed seeded sample of "
+                         "the rows, listed in DIR/<name>_rows.npy)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave out the CPU baselines and the parity record")
     ap.add_argument("--overlap-streams", action="store_true",
-                    help="also time the same batch launched on two streams in turn (each "
-                         "launch with its own v_out / workspace, consecutive launches "
+                    help="with --full: also time the same batch launched on two streams in "
+                         "turn (each launch with its own v_out / workspace, consecutive launches "
                          "overlapping): reported beside the line as overlapped_streams, "
                          "never its value (DESIGN.md §6, one launch and what concurrency "
                          "recovers)")
     ap.add_argument("--pcie-launches", type=int, default=2,
-                    help="launches timed through the host-array ABI (pcie_inclusive; 0: skip)")
+                    help="with --full: launches timed through the host-array ABI "
+                         "(pcie_inclusive; 0: skip)")
     ap.add_argument("--dry-run", action="store_true",
                     help="exercise the rank spawn / gloo / timing / gather plumbing without "
                          "a GPU (no march; the line is marked dry_run and is not a measurement)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.overlap_streams and not args.full:
+        ap.error("--overlap-streams is one of the --full measurements: add --full")
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -665,8 +730,13 @@ def run_rank(args):
     # the PCIe-inclusive rate of the host-array boundary (fdcn_it_batch /
     # fdcn_cn_batch with NumPy arrays: H2D of the plan, the march, D2H of
     # v_out): reported beside the line, never its value
+    dumped = None
+    if args.dump_outputs:  # this rank's v_out of the last timed launch
+        dumped = dump_outputs(args.dump_outputs, {"v_out": res},
+                              f"_rank{rank}" if world > 1 else "")
+
     pcie = None
-    if rank == 0 and world == 1 and args.pcie_launches > 0 and not args.total:
+    if args.full and rank == 0 and world == 1 and args.pcie_launches > 0 and not args.total:
         # the caller's v_out buffer, reused across launches as a caller
         # launching repeatedly would (a fresh 82 MB array per call pays ~20 k
         # first-touch page faults inside the D2H copy)
@@ -732,9 +802,9 @@ def run_rank(args):
                               "one's end; value is one launch at a time"}
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, parity = cpu_baseline(g, args.cpu_seconds, res)
-    elif world > 1 and not args.no_cpu_baseline:
+    elif args.full and world > 1 and not args.no_cpu_baseline:
         # every rank checks a sample of its own timed output against the C
         # oracle on its host cores; the record is the worst over the ranks
         parity = reduce_parity(sample_parity(g, res, PARITY_SAMPLE), world, cdev)
@@ -791,6 +861,8 @@ def run_rank(args):
             "parity": parity,
             "host_build_s": t_build,
             "cpu_baseline": cpu,
+            "full": args.full,
+            "dumped_outputs": dumped,
         }
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -890,6 +962,7 @@ def bench_scenario_file(args):
     avg = {k: sum(v) / len(v) * 1e3 for k, v in parts.items()}
     march_ms = avg["march"]
     n_pde = sum(1 for b in bt if b != "none")
+    dumped = dump_outputs(args.dump_outputs, out) if args.dump_outputs else None
     print(json.dumps({
         "metric": "scenario file wall time (run_all_scenarios pricing)",
         "value": ms, "unit": "ms/file", "n_gpus": 1, "steps": args.steps,
@@ -903,7 +976,8 @@ def bench_scenario_file(args):
                                              n_pde // scenario_batch.CHUNK_ROWS))},
         "host_ms": ms - march_ms, "plan_ms": avg["plan"], "march_and_epilogue_ms": march_ms,
         "host_parts_ms": {k: avg[k] for k in ("prep", "plan", "free") if k in avg},
-        "outputs_finite": bool(np.all(np.isfinite(out["model_price"])))}), flush=True)
+        "outputs_finite": bool(np.all(np.isfinite(out["model_price"]))),
+        "full": args.full, "dumped_outputs": dumped}), flush=True)
 
 
 def bench_american_file(args):
@@ -944,6 +1018,7 @@ def bench_american_file(args):
     avg = {k: sum(v) / len(v) * 1e3 for k, v in parts.items()}
     march_ms = avg["march"]
     node_steps = R * (5 * N * M + N * 2 * M)  # N, sigma +-h, +-2h at M steps; 2M
+    dumped = dump_outputs(args.dump_outputs, out) if args.dump_outputs else None
     print(json.dumps({
         "metric": "American scenario file wall time (run_all_american_scenarios pricing)",
         "value": ms, "unit": "ms/file", "n_gpus": 1, "steps": args.steps,
@@ -958,7 +1033,8 @@ def bench_american_file(args):
         "host_ms": ms - march_ms, "plan_ms": avg["plan"], "march_and_epilogue_ms": march_ms,
         "host_parts_ms": {k: avg[k] for k in ("prep", "plan", "free") if k in avg},
         "node_steps_per_s": node_steps / (ms * 1e-3),
-        "outputs_finite": bool(np.all(np.isfinite(out["model_price"])))}), flush=True)
+        "outputs_finite": bool(np.all(np.isfinite(out["model_price"]))),
+        "full": args.full, "dumped_outputs": dumped}), flush=True)
 
 
 def bench_trade(args):
@@ -1040,7 +1116,8 @@ def bench_trade(args):
     times.sort()
     ms = sum(times) / len(times) * 1e3
     cfg["solves_per_trade"] = solves
-    if args.workload == "trade_double":  # the same trade on the whole grid
+    dumped = dump_outputs(args.dump_outputs, res) if args.dump_outputs else None
+    if args.full and args.workload == "trade_double":  # the same trade on the whole grid
         full = []
         for _ in range(max(1, args.steps // 2)):
             t0 = time.perf_counter()
@@ -1055,7 +1132,8 @@ def bench_trade(args):
         "ms_median": times[len(times) // 2] * 1e3, "higher_is_better": False,
         "scaling": "none", "vs_baseline": None, "dtype": "f64",
         "data": "the reference's own trade parameters", "config": cfg,
-        "node_steps_per_s": node_steps / (ms * 1e-3), "result": res}), flush=True)
+        "node_steps_per_s": node_steps / (ms * 1e-3), "result": res,
+        "full": args.full, "dumped_outputs": dumped}), flush=True)
 
 
 def build_spot_vc(B: int, n_space: int, n_time: int, seed: int = 0):
@@ -1172,8 +1250,9 @@ def bench_spot_vc(args):
     elapsed = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / max(1, args.steps)
     res = out.cpu().numpy()
+    dumped = dump_outputs(args.dump_outputs, {"v_out": res}) if args.dump_outputs else None
     cpu = parity = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cpu, parity = vc_cpu_baseline(g, args.cpu_seconds, res)
     units = g.n_nodes - 1
     node_steps = g.B * units * g.n_time
@@ -1224,7 +1303,8 @@ def bench_spot_vc(args):
                    "slots": slots, "slot_use": g.n_nodes / slots},
         "outputs_finite": bool(np.all(np.isfinite(res))), "parity": parity,
         "out_sha": hashlib.sha256(np.ascontiguousarray(res).tobytes()).hexdigest()[:16],
-        "host_build_s": t_build, "cpu_baseline": cpu}), flush=True)
+        "host_build_s": t_build, "cpu_baseline": cpu,
+        "full": args.full, "dumped_outputs": dumped}), flush=True)
     if parity is not None and not (parity["ok"] and parity["all_finite"]):
         print(f"bench.py: PARITY FAILURE {parity}", file=sys.stderr, flush=True)
         return 3
@@ -1274,8 +1354,10 @@ def bench_analytic(args):
     elapsed = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / max(1, args.steps)
     got = price.cpu().numpy()
+    dumped = (dump_outputs(args.dump_outputs, {"price": got, "vanilla": van.cpu().numpy()})
+              if args.dump_outputs else None)
     cpu = None
-    if not args.no_cpu_baseline:  # the host engine (Python/NumPy/SciPy), one core
+    if args.full and not args.no_cpu_baseline:  # the host engine (Python/NumPy/SciPy), one core
         n, t_cpu = 0, 0.0
         names = ("s", "b", "r", "t", "x", "sigma", "h", "k")
         while t_cpu < min(args.cpu_seconds, 5.0) and n < B:
@@ -1304,7 +1386,7 @@ def bench_analytic(args):
         "roofline": {"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": gbs / HBM_PEAK_GBS, "traffic": None},
         "kernel_ms_per_launch": kernel_ms, "outputs_finite": bool(np.all(np.isfinite(got))),
-        "cpu_baseline": cpu}), flush=True)
+        "cpu_baseline": cpu, "full": args.full, "dumped_outputs": dumped}), flush=True)
 
 
 def main(argv=None):

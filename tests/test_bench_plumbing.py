@@ -356,3 +356,46 @@ def test_reduce_parity_over_eight_ranks(tmp_path):
         assert not bad["ok"] and bad["max_rel_err"] > bench.PARITY_TOL and bad["n_compared"] == 16
         assert "worst over the 8 ranks" in bad["rule"]
     assert all(r[1] == recs[0][1] for r in recs)
+
+
+def test_plain_and_full_arguments():
+    """A plain run asks for none of the --full measurements; --overlap-streams
+    is one of them and is refused without --full; --steps is at least 1."""
+    import pytest
+    sys.path.insert(0, ROOT)
+    import bench
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not plain.full and plain.dump_outputs == "" and plain.steps == 7 and plain.warmup == 2
+    full = bench.parse(["--full", "--overlap-streams", "--dump-outputs", "d"])
+    assert full.full and full.overlap_streams and full.dump_outputs == "d"
+    for bad in (["--overlap-streams"], ["--steps", "0"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_dump_outputs_writes_float64_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: numeric entries as float64 .npy, text columns left
+    out; above the cap a seeded sample of the rows, the same on every run,
+    whose indices are written beside it and whose total stays under the cap."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    v = np.arange(40 * 16, dtype=np.float64).reshape(40, 16)
+    arrays = {"v_out": v, "price": np.float32(1.5), "names": np.array(["a", "b"], dtype=object),
+              "label": "text", "count": [1, 2, 3]}
+    rec = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert sorted(rec) == ["count", "price", "v_out"]
+    got = np.load(tmp_path / "a" / "v_out.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, v)
+    assert rec["v_out"]["sampled_rows"] is None
+    assert np.load(tmp_path / "a" / "price.npy") == 1.5
+    assert sorted(os.listdir(tmp_path / "a")) == ["count.npy", "price.npy", "v_out.npy"]
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", v.nbytes // 4)
+    recs = [bench.dump_outputs(str(tmp_path / d), {"v_out": v}, "_rank1") for d in ("b", "c")]
+    rows = np.load(tmp_path / "b" / "v_out_rows_rank1.npy")
+    got = np.load(tmp_path / "b" / "v_out_rank1.npy")
+    assert rows.dtype == np.float64 and 1 <= len(rows) == recs[0]["v_out_rank1"]["sampled_rows"]
+    assert np.all(np.diff(rows) > 0) and np.array_equal(got, v[rows.astype(int)])
+    assert got.nbytes <= v.nbytes // 4
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "v_out_rows_rank1.npy"))
+    assert np.array_equal(got, np.load(tmp_path / "c" / "v_out_rank1.npy"))

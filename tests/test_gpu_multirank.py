@@ -13,7 +13,7 @@ N > 1 code path runs on the HIP engine end to end:
     the world-size-1 GPU run (`==`: both plans pick the same kernel
     instance, asserted), and a sample of rows equals the oracle-engine run
     within the GPU-vs-oracle bounds;
-  * bench.py --gpus 2 --workload barrier --total N --backend gloo: the
+  * bench.py --full --gpus 2 --workload barrier --total N --backend gloo: the
     config-4 strong-scaling launch itself, with its reduced parity record
     (every rank's first scenarios against the C oracle) ok.
 """
@@ -139,7 +139,8 @@ def test_bench_total_two_ranks_gloo_parity_ok(tmp_path):
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(v, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload",
-           "barrier", "--total", "2000", "--backend", "gloo", "--steps", "2", "--warmup", "1"]
+           "barrier", "--total", "2000", "--backend", "gloo", "--steps", "2", "--warmup", "1",
+           "--full"]  # the parity record is one of the --full checks
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

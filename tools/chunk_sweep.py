@@ -19,7 +19,7 @@ def main():
     for rows, mx in sweep:
         mod.CHUNK_ROWS, mod.MAX_CHUNKS = rows, mx
         args = types.SimpleNamespace(batch=None, n_space=None, n_time=None, steps=5 if am else 10,
-                                     warmup=2 if am else 3)
+                                     warmup=2 if am else 3, full=False, dump_outputs="")
         import io
         import contextlib
         buf = io.StringIO()

@@ -14,7 +14,8 @@ def main():
     wl, out = sys.argv[1], sys.argv[2]
     fn = {"scenario_file": bench.bench_scenario_file,
           "american_file": bench.bench_american_file}[wl]
-    args = types.SimpleNamespace(batch=None, n_space=None, n_time=None, steps=3, warmup=3)
+    args = types.SimpleNamespace(batch=None, n_space=None, n_time=None, steps=3, warmup=3,
+                                 full=False, dump_outputs="")
     fn(args)  # imports, first-call costs
     pr = cProfile.Profile()
     args.steps, args.warmup = 10, 0
