@@ -30,7 +30,7 @@ P_HI_C0, P_HI_E0, P_HI_C1, P_HI_E1 = 9, 10, 11, 12
 NPARAM = 13
 I_LO_FORM, I_HI_FORM, I_KO_LO, I_KO_HI, I_MON_START, I_MON_COUNT, I_TAU_MODE = range(7)
 NIPARAM = 7
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 EXPORTED = ("fdcn_cn_batch", "fdcn_it_batch", "fdcn_cn_batch_dev", "fdcn_it_batch_dev",
             "fdcn_plan", "fdcn_sm_extent", "fdcn_log_grid", "fdcn_dividend_jump",
@@ -43,14 +43,22 @@ EXPORTED = ("fdcn_cn_batch", "fdcn_it_batch", "fdcn_cn_batch_dev", "fdcn_it_batc
             "fdcn_session_march",
             "fdcn_session_dividend_jump", "fdcn_session_greeks", "fdcn_session_fetch",
             "fdcn_vc_batch", "fdcn_vc_batch_dev", "fdcn_vc_plan", "fdcn_barrier_plan",
-            "fdcn_vmath", "fdcn_american_plan", "fdcn_device_ordinals")
+            "fdcn_vmath", "fdcn_american_plan", "fdcn_device_ordinals",
+            "fdcn_mc_barrier_batch", "fdcn_mc_barrier_batch_dev", "fdcn_mc_plan")
 # include/fdcn_diag.h: test / tuning entry points, not the product boundary
 DIAG_EXPORTED = ("fdcn_force_variant", "fdcn_forced_variant", "fdcn_variant_name",
-                 "fdcn_vc_force_variant", "fdcn_vc_variant_name", "fdcn_vc_forms")
+                 "fdcn_vc_force_variant", "fdcn_vc_variant_name", "fdcn_vc_forms",
+                 "fdcn_mc_normals")
 FLAVOUR_THROUGHPUT, FLAVOUR_LATENCY, FLAVOUR_PAIRED = 0, 1, 2
 VC_NDIAG = 6
 RR_NPARAM, RR_NFLAG = 8, 5
 DB_NPARAM, DB_NFLAG = 8, 3
+# Monte Carlo discrete barrier (enum fdcn_mc_param / _flag / _step)
+MC_NPARAM, MC_NFLAG, MC_NSTEP, MC_NSTAT = 6, 5, 5, 4
+MC_P_SPOT, MC_P_STRIKE, MC_P_DF_T, MC_P_THRESHOLD, MC_P_REBATE, MC_P_FLOOR = range(6)
+MC_F_PUT, MC_F_KIND, MC_F_REBATE_AT_HIT, MC_F_DIV_FIRST, MC_F_STREAM = range(5)
+MC_S_DRIFT, MC_S_DIFF, MC_S_DIV, MC_S_MONITOR, MC_S_DF_END = range(5)
+MC_KIND = {"none": 0, "down-and-out": 1, "up-and-out": 2, "down-and-in": 3, "up-and-in": 4}
 
 
 class FdcnError(RuntimeError):
@@ -236,6 +244,16 @@ def lib() -> ctypes.CDLL:
             L.fdcn_vc_variant_name.argtypes = [_I, _I, ctypes.c_char_p, _I]
             L.fdcn_vc_forms.restype = _I
             L.fdcn_vc_forms.argtypes = [_I, _I, _I, _I, _PD, _PI]
+            L.fdcn_mc_barrier_batch.restype = _I
+            L.fdcn_mc_barrier_batch.argtypes = [_I, _I, _I64, _I, _V, _V, _V, _V, ctypes.c_uint64,
+                                                _I64, _V, _V]
+            L.fdcn_mc_barrier_batch_dev.restype = _I
+            L.fdcn_mc_barrier_batch_dev.argtypes = [_I, _I, _I64, _I, _V, _V, _V, _V,
+                                                    ctypes.c_uint64, _I64, _V, _V, _V, _I64, _V]
+            L.fdcn_mc_plan.restype = _I
+            L.fdcn_mc_plan.argtypes = [_I64, _PI, _PI, ctypes.POINTER(ctypes.c_int64)]
+            L.fdcn_mc_normals.restype = _I
+            L.fdcn_mc_normals.argtypes = [_I64, _I, ctypes.c_uint64, _I, _I64, _V]
             _lib = L
     return _lib
 
@@ -604,3 +622,68 @@ def dividend_jump(s_nodes, v, cash_div: float, strike_call: float = -1.0) -> np.
         msg = lib().fdcn_last_error().decode(errors="replace")
         raise ValueError(msg)
     return out
+
+
+def mc_plan(n_obs: int) -> dict:
+    """Geometry of a Monte Carlo launch of n_obs observations per contract
+    (fdcn_mc_plan; host only): workgroups per contract, observations per
+    workgroup, workspace bytes per contract."""
+    nb, per = ctypes.c_int32(), ctypes.c_int32()
+    ws = ctypes.c_int64()
+    _check(lib().fdcn_mc_plan(int(n_obs), ctypes.byref(nb), ctypes.byref(per), ctypes.byref(ws)))
+    return dict(blocks_per_contract=nb.value, obs_per_block=per.value,
+                ws_bytes_per_contract=ws.value)
+
+
+def mc_barrier_batch(params, flags, step, n_obs: int, antithetic: bool, *, z=None, seed: int = 0,
+                     obs_first: int = 0, want_payoffs: bool = False):
+    """fdcn_mc_barrier_batch on host arrays -> stats [B, MC_NSTAT] (price,
+    stderr, sum p, sum p^2), or (stats, payoffs [B, n_obs]) with want_payoffs.
+    params [B, MC_NPARAM], flags [B, MC_NFLAG], step [B, n_steps, MC_NSTEP];
+    z [n_obs, n_steps] supplies the normals, None generates them on the device
+    (Philox, include/fdcn.h) from `seed`, the contracts' stream ids and
+    `obs_first`."""
+    require_device()
+    P = _f64(params).reshape(-1, MC_NPARAM)
+    F = _i32(flags).reshape(-1, MC_NFLAG)
+    S = _f64(step)
+    B = P.shape[0]
+    if F.shape[0] != B or S.ndim != 3 or S.shape[0] != B or S.shape[2] != MC_NSTEP:
+        raise ValueError("mc_barrier_batch: params [B, 6], flags [B, 5], step [B, n_steps, 5]")
+    n_steps = S.shape[1]
+    Z = None
+    if z is not None:
+        Z = _f64(z)
+        if Z.shape != (int(n_obs), n_steps):
+            raise ValueError(f"mc_barrier_batch: z must be [n_obs, n_steps] = {(n_obs, n_steps)}")
+    stats = np.empty((B, MC_NSTAT), dtype=np.float64)
+    pay = np.empty((B, int(n_obs)), dtype=np.float64) if want_payoffs else None
+    _check(lib().fdcn_mc_barrier_batch(
+        B, n_steps, int(n_obs), 1 if antithetic else 0, P.ctypes.data, F.ctypes.data,
+        S.ctypes.data, Z.ctypes.data if Z is not None else None, int(seed) & (2 ** 64 - 1),
+        int(obs_first), stats.ctypes.data, pay.ctypes.data if want_payoffs else None))
+    return (stats, pay) if want_payoffs else stats
+
+
+def mc_barrier_batch_dev(B: int, n_steps: int, n_obs: int, antithetic: bool, params_ptr: int,
+                         flags_ptr: int, step_ptr: int, z_ptr: Optional[int], seed: int,
+                         obs_first: int, stats_ptr: int, payoff_ptr: Optional[int],
+                         workspace_ptr: Optional[int], workspace_bytes: int,
+                         stream_ptr: Optional[int]) -> None:
+    """fdcn_mc_barrier_batch_dev: every array already on the device;
+    asynchronous on `stream_ptr`."""
+    _check(lib().fdcn_mc_barrier_batch_dev(
+        int(B), int(n_steps), int(n_obs), 1 if antithetic else 0, params_ptr, flags_ptr, step_ptr,
+        z_ptr, int(seed) & (2 ** 64 - 1), int(obs_first), stats_ptr, payoff_ptr, workspace_ptr,
+        int(workspace_bytes), stream_ptr))
+
+
+def mc_normals(n_obs: int, n_steps: int, seed: int, stream_id: int = 0,
+               obs_first: int = 0) -> np.ndarray:
+    """The normals the path kernel generates (diagnostics, include/fdcn_diag.h)
+    -> z [n_obs, n_steps]."""
+    require_device()
+    z = np.empty((int(n_obs), int(n_steps)), dtype=np.float64)
+    _check(lib().fdcn_mc_normals(int(n_obs), int(n_steps), int(seed) & (2 ** 64 - 1),
+                                 int(stream_id), int(obs_first), z.ctypes.data))
+    return z

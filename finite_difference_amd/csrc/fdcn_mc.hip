@@ -1,0 +1,453 @@
+// fdcn_mc.hip -- Monte Carlo discrete-barrier pricer for gfx950.
+//
+// The cross-check of the FD barrier engines: price_discrete_barrier_mc of
+// mc_discrete_barrier_option.py (:225-424).  One launch prices B contracts
+// that share n_steps, n_obs and the antithetic switch; everything else is per
+// contract.  A path's whole state is one double, so nothing touches memory
+// except the per-step table (uniform across a workgroup: scalar loads), the
+// optional supplied normals and the optional payoff dump.  fp64 throughout.
+//
+//   mc_path_kernel<ANTI, GEN>  one workgroup = kChunk consecutive
+//                              observations of one contract; each thread
+//                              walks kPerThread of them and keeps sum(p),
+//                              sum(p^2) in index order; fixed LDS tree; one
+//                              partial pair per workgroup into the workspace
+//   mc_finalize_kernel         one thread per contract adds the partials in
+//                              block order and writes price / stderr (:407-410)
+//   mc_normals_kernel          the generator alone (include/fdcn_diag.h)
+//
+// No floating-point atomics: the chunk is a function of n_obs only and the
+// tree is fixed, so a contract's result depends on neither B, its position in
+// the batch, nor how the workgroups were scheduled.
+//
+// The path functional keeps the reference's operation order (simulate_payoffs,
+// :314-387) with separately rounded multiply and add (contraction off), so on
+// supplied normals it differs from NumPy only through the device exp.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/fdcn.h"
+#include "../../include/fdcn_diag.h"
+
+#pragma clang fp contract(off)
+
+namespace fdcn_internal {
+int set_error(int code, const char* msg);     // fdcn_kernels.hip (fdcn_last_error)
+int thread_stream(hipStream_t* out);          // fdcn_kernels.hip (one per thread, device)
+}
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kPerThread = 16;
+constexpr int kChunk = kThreads * kPerThread;  // observations per workgroup
+
+// ---- Philox4x32-10 (Salmon et al., SC'11; Random123 constants) ------------
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                              uint32_t k0, uint32_t k1, uint32_t x[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  x[0] = c0;
+  x[1] = c1;
+  x[2] = c2;
+  x[3] = c3;
+}
+
+// 53 bits of two words -> (0, 1]: ((hi >> 5) 2^26 + (lo >> 6) + 0.5) 2^-53
+__device__ __forceinline__ double u53(uint32_t hi, uint32_t lo) {
+  return ((double)(hi >> 5) * 67108864.0 + (double)(lo >> 6) + 0.5) * 0x1p-53;
+}
+
+// The normals z[2j], z[2j+1] of observation `obs` (the mapping of fdcn.h).
+__device__ __forceinline__ void normal_pair(uint64_t obs, uint32_t j, uint32_t stream,
+                                            uint64_t seed, double& z0, double& z1) {
+  uint32_t x[4];
+  philox4x32_10((uint32_t)obs, (uint32_t)(obs >> 32), j, stream, (uint32_t)seed,
+                (uint32_t)(seed >> 32), x);
+  const double u1 = u53(x[0], x[1]);
+  const double u2 = u53(x[2], x[3]);
+  const double r = sqrt(-2.0 * log(u1));
+  double sn, cs;
+  sincospi(2.0 * u2, &sn, &cs);
+  z0 = r * cs;
+  z1 = r * sn;
+}
+
+// ---- one path --------------------------------------------------------------
+struct Contract {
+  double spot, strike, df_T, thr, rebate, floor;
+  int kind;  // 0 none, 1 down-out, 2 up-out, 3 down-in, 4 up-in
+  bool put, down, rebate_at_hit, div_first;
+};
+
+struct Path {
+  double s, hit_df;
+  bool untouched;  // no monitored breach so far
+};
+
+// step row: drift, diff, cash dividend, monitor flag, df at the step's end
+__device__ __forceinline__ void advance(Path& p, const Contract& c, const double* __restrict__ st,
+                                        double z) {
+  p.s *= exp(st[0] + st[1] * z);
+  const double div = st[2];
+  if (c.div_first && div != 0.0) p.s = fmax(p.s - div, c.floor);
+  if (c.kind != 0 && st[3] != 0.0) {
+    const bool breached = c.down ? p.s <= c.thr : p.s >= c.thr;
+    if (breached && p.untouched) {
+      p.hit_df = st[4];  // the first hit's own discount factor
+      p.untouched = false;
+    }
+  }
+  if (!c.div_first && div != 0.0) p.s = fmax(p.s - div, c.floor);
+}
+
+__device__ __forceinline__ double payoff(const Path& p, const Contract& c) {
+  const double vanilla = c.put ? fmax(c.strike - p.s, 0.0) : fmax(p.s - c.strike, 0.0);
+  const double pv = c.df_T * vanilla;
+  if (c.kind == 0) return pv;
+  if (c.kind <= 2)  // knock-out: survivors the vanilla, the others the rebate
+    return p.untouched ? pv : c.rebate * (c.rebate_at_hit ? p.hit_df : c.df_T);
+  return p.untouched ? 0.0 : pv;  // knock-in
+}
+
+struct McArgs {
+  int32_t n_steps, n_blocks;
+  int64_t n_obs, obs_first;
+  uint64_t seed;
+};
+
+// The arrays are separate __restrict__ arguments: with the inputs known not to
+// alias the payoff dump, the per-step table (uniform across a workgroup) is
+// read with scalar loads.
+template <bool ANTI, bool GEN>
+__global__ void __launch_bounds__(kThreads)
+mc_path_kernel(McArgs a, const double* __restrict__ params, const int32_t* __restrict__ flags,
+               const double* __restrict__ step, const double* __restrict__ z,
+               double* __restrict__ ws, double* __restrict__ payoff_out) {
+  const int b = blockIdx.x / a.n_blocks;    // contract
+  const int blk = blockIdx.x % a.n_blocks;  // chunk of observations
+  const int tid = threadIdx.x;
+  const double* P = params + (size_t)b * FDCN_MC_NPARAM;
+  const int32_t* F = flags + (size_t)b * FDCN_MC_NFLAG;
+  const double* S = step + (size_t)b * a.n_steps * FDCN_MC_NSTEP;
+  Contract c;
+  c.spot = P[FDCN_MC_P_SPOT];
+  c.strike = P[FDCN_MC_P_STRIKE];
+  c.df_T = P[FDCN_MC_P_DF_T];
+  c.thr = P[FDCN_MC_P_THRESHOLD];
+  c.rebate = P[FDCN_MC_P_REBATE];
+  c.floor = P[FDCN_MC_P_FLOOR];
+  c.put = F[FDCN_MC_F_PUT] != 0;
+  c.kind = F[FDCN_MC_F_KIND];
+  if (c.kind < 0 || c.kind > 4) c.kind = 0;  // _dev callers: the host entry rejects these
+  c.down = c.kind == 1 || c.kind == 3;
+  c.rebate_at_hit = F[FDCN_MC_F_REBATE_AT_HIT] != 0;
+  c.div_first = F[FDCN_MC_F_DIV_FIRST] != 0;
+  const uint32_t stream = (uint32_t)F[FDCN_MC_F_STREAM];
+
+  double sum = 0.0, sum2 = 0.0;
+  for (int k = 0; k < kPerThread; ++k) {
+    const int64_t i = (int64_t)blk * kChunk + (int64_t)k * kThreads + tid;
+    if (i >= a.n_obs) break;
+    Path up{c.spot, c.df_T, true}, dn{c.spot, c.df_T, true};
+    const double* zi = GEN ? nullptr : z + (size_t)i * a.n_steps;
+    for (int m = 0; m < a.n_steps; m += 2) {
+      double z0, z1 = 0.0;
+      if (GEN) {
+        normal_pair((uint64_t)(a.obs_first + i), (uint32_t)(m >> 1), stream, a.seed, z0, z1);
+      } else {
+        z0 = zi[m];
+        if (m + 1 < a.n_steps) z1 = zi[m + 1];
+      }
+      advance(up, c, S + (size_t)m * FDCN_MC_NSTEP, z0);
+      if (ANTI) advance(dn, c, S + (size_t)m * FDCN_MC_NSTEP, -z0);
+      if (m + 1 < a.n_steps) {
+        advance(up, c, S + (size_t)(m + 1) * FDCN_MC_NSTEP, z1);
+        if (ANTI) advance(dn, c, S + (size_t)(m + 1) * FDCN_MC_NSTEP, -z1);
+      }
+    }
+    double p = payoff(up, c);
+    if (ANTI) p = 0.5 * (p + payoff(dn, c));
+    if (payoff_out) payoff_out[(size_t)b * (size_t)a.n_obs + (size_t)i] = p;
+    sum += p;
+    sum2 += p * p;
+  }
+
+  __shared__ double sh[2][kThreads];
+  sh[0][tid] = sum;
+  sh[1][tid] = sum2;
+  __syncthreads();
+  for (int off = kThreads / 2; off > 0; off >>= 1) {
+    if (tid < off) {
+      sh[0][tid] += sh[0][tid + off];
+      sh[1][tid] += sh[1][tid + off];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    double* w = ws + ((size_t)b * a.n_blocks + blk) * 2;
+    w[0] = sh[0][0];
+    w[1] = sh[1][0];
+  }
+}
+
+// stats[b] = price, stderr, sum p, sum p^2 (:407-410)
+__global__ void __launch_bounds__(kThreads) mc_finalize_kernel(int32_t B, int32_t n_blocks,
+                                                               int64_t n_obs,
+                                                               const double* __restrict__ ws,
+                                                               double* __restrict__ stats) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const double* w = ws + (size_t)b * n_blocks * 2;
+  double sum = 0.0, sum2 = 0.0;
+  for (int k = 0; k < n_blocks; ++k) {
+    sum += w[2 * k];
+    sum2 += w[2 * k + 1];
+  }
+  const double n = (double)n_obs;
+  const double price = sum / n;
+  const double var = fmax(0.0, sum2 / n - price * price);
+  double* o = stats + (size_t)b * FDCN_MC_NSTAT;
+  o[0] = price;
+  o[1] = sqrt(var / n);
+  o[2] = sum;
+  o[3] = sum2;
+}
+
+__global__ void __launch_bounds__(kThreads) mc_normals_kernel(int64_t n_obs, int32_t n_steps,
+                                                              uint64_t seed, uint32_t stream,
+                                                              int64_t obs_first,
+                                                              double* __restrict__ z) {
+  const int64_t n_pairs = (n_steps + 1) / 2;
+  const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (t >= n_obs * n_pairs) return;
+  const int64_t i = t / n_pairs;
+  const int64_t j = t % n_pairs;
+  double z0, z1;
+  normal_pair((uint64_t)(obs_first + i), (uint32_t)j, stream, seed, z0, z1);
+  double* zi = z + (size_t)i * n_steps;
+  zi[2 * j] = z0;
+  if (2 * j + 1 < n_steps) zi[2 * j + 1] = z1;  // an odd n_steps drops the last sine
+}
+
+// ---- host side -------------------------------------------------------------
+int mfail(int code, const char* msg) { return fdcn_internal::set_error(code, msg); }
+
+int64_t blocks_for(int64_t n_obs) { return (n_obs + kChunk - 1) / kChunk; }
+
+// sizes every entry point checks, before any device call
+int check_sizes(int32_t B, int32_t n_steps, int64_t n_obs, int32_t antithetic) {
+  if (B < 1) return mfail(FDCN_EINVAL, "mc_barrier_batch: B must be >= 1");
+  if (n_steps < 1) return mfail(FDCN_EINVAL, "mc_barrier_batch: n_steps must be >= 1");
+  if (n_obs < 1) return mfail(FDCN_EINVAL, "mc_barrier_batch: n_obs must be >= 1");
+  if (antithetic < 0 || antithetic > 1)
+    return mfail(FDCN_EINVAL, "mc_barrier_batch: antithetic must be 0 or 1");
+  if (n_obs > ((int64_t)1 << 40) || blocks_for(n_obs) * (int64_t)B > 0x7fffffffLL)
+    return mfail(FDCN_EINVAL, "mc_barrier_batch: B * n_obs is beyond one launch's grid");
+  return FDCN_OK;
+}
+
+int check_contracts(int32_t B, const double* params, const int32_t* flags) {
+  char msg[160];
+  for (int32_t b = 0; b < B; ++b) {
+    const int32_t* f = flags + (size_t)b * FDCN_MC_NFLAG;
+    const double* p = params + (size_t)b * FDCN_MC_NPARAM;
+    const char* bad = nullptr;
+    if (f[FDCN_MC_F_PUT] < 0 || f[FDCN_MC_F_PUT] > 1) bad = "flag put must be 0 or 1";
+    else if (f[FDCN_MC_F_KIND] < 0 || f[FDCN_MC_F_KIND] > 4) bad = "flag kind must be 0..4";
+    else if (f[FDCN_MC_F_REBATE_AT_HIT] < 0 || f[FDCN_MC_F_REBATE_AT_HIT] > 1)
+      bad = "flag rebate_at_hit must be 0 or 1";
+    else if (f[FDCN_MC_F_DIV_FIRST] < 0 || f[FDCN_MC_F_DIV_FIRST] > 1)
+      bad = "flag dividend_before_monitor must be 0 or 1";
+    else if (f[FDCN_MC_F_STREAM] < 0) bad = "flag stream id must be >= 0";
+    else if (!(p[FDCN_MC_P_SPOT] > 0.0)) bad = "spot must be positive";
+    else if (!(p[FDCN_MC_P_STRIKE] > 0.0)) bad = "strike must be positive";
+    else if (f[FDCN_MC_F_KIND] != 0 && !(p[FDCN_MC_P_THRESHOLD] > 0.0))
+      bad = "threshold must be positive where a barrier is set";
+    if (bad) {
+      snprintf(msg, sizeof msg, "mc_barrier_batch: contract %d: %s", b, bad);
+      return mfail(FDCN_EINVAL, msg);
+    }
+  }
+  return FDCN_OK;
+}
+
+int launch(int32_t B, int32_t n_steps, int64_t n_obs, int32_t antithetic, const double* params,
+           const int32_t* flags, const double* step, const double* z, uint64_t seed,
+           int64_t obs_first, double* stats, double* payoff_out, double* workspace,
+           hipStream_t stream) {
+  McArgs a;
+  a.n_steps = n_steps;
+  a.n_blocks = (int32_t)blocks_for(n_obs);
+  a.n_obs = n_obs;
+  a.obs_first = obs_first;
+  a.seed = seed;
+  const dim3 grid((uint32_t)((int64_t)a.n_blocks * B)), block(kThreads);
+  auto fn = antithetic ? (z ? mc_path_kernel<true, false> : mc_path_kernel<true, true>)
+                       : (z ? mc_path_kernel<false, false> : mc_path_kernel<false, true>);
+  hipLaunchKernelGGL(fn, grid, block, 0, stream, a, params, flags, step, z, workspace,
+                     payoff_out);
+  if (hipGetLastError() != hipSuccess) return mfail(FDCN_EHIP, "mc_barrier_batch: launch failed");
+  hipLaunchKernelGGL(mc_finalize_kernel, dim3((B + kThreads - 1) / kThreads), block, 0, stream, B,
+                     a.n_blocks, n_obs, workspace, stats);
+  if (hipGetLastError() != hipSuccess) return mfail(FDCN_EHIP, "mc_barrier_batch: launch failed");
+  return FDCN_OK;
+}
+
+size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+
+}  // namespace
+
+extern "C" {
+
+int fdcn_mc_plan(int64_t n_obs, int32_t* blocks_per_contract, int32_t* obs_per_block,
+                 int64_t* ws_bytes_per_contract) {
+  if (n_obs < 1 || n_obs > ((int64_t)1 << 40))
+    return mfail(FDCN_EINVAL, "mc_plan: n_obs must be in 1 .. 2^40");
+  const int64_t nb = blocks_for(n_obs);
+  if (blocks_per_contract) *blocks_per_contract = (int32_t)nb;
+  if (obs_per_block) *obs_per_block = kChunk;
+  if (ws_bytes_per_contract) *ws_bytes_per_contract = nb * 2 * (int64_t)sizeof(double);
+  return FDCN_OK;
+}
+
+int fdcn_mc_barrier_batch_dev(int32_t B, int32_t n_steps, int64_t n_obs, int32_t antithetic,
+                              const double* params, const int32_t* flags, const double* step,
+                              const double* z, uint64_t seed, int64_t obs_first, double* stats,
+                              double* payoff_out, double* workspace, int64_t workspace_bytes,
+                              void* stream) {
+  int rc = check_sizes(B, n_steps, n_obs, antithetic);
+  if (rc) return rc;
+  if (!params) return mfail(FDCN_EINVAL, "mc_barrier_batch_dev: params is NULL");
+  if (!flags) return mfail(FDCN_EINVAL, "mc_barrier_batch_dev: flags is NULL");
+  if (!step) return mfail(FDCN_EINVAL, "mc_barrier_batch_dev: step is NULL");
+  if (!stats) return mfail(FDCN_EINVAL, "mc_barrier_batch_dev: stats is NULL");
+  const int64_t need = blocks_for(n_obs) * 2 * (int64_t)sizeof(double) * B;
+  if (workspace && workspace_bytes < need) {
+    char msg[160];
+    snprintf(msg, sizeof msg,
+             "mc_barrier_batch_dev: workspace of %lld B is smaller than the %lld B this launch "
+             "needs (fdcn_mc_plan)", (long long)workspace_bytes, (long long)need);
+    return mfail(FDCN_EINVAL, msg);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  bool own = false;
+  if (!workspace) {  // stream-ordered scratch, released after the launch
+    if (hipMallocAsync((void**)&workspace, (size_t)need, s) != hipSuccess)
+      return mfail(FDCN_ENOMEM, "mc_barrier_batch_dev: hipMallocAsync failed");
+    own = true;
+  }
+  rc = launch(B, n_steps, n_obs, antithetic, params, flags, step, z, seed, obs_first, stats,
+              payoff_out, workspace, s);
+  if (own) (void)hipFreeAsync(workspace, s);
+  return rc;
+}
+
+int fdcn_mc_barrier_batch(int32_t B, int32_t n_steps, int64_t n_obs, int32_t antithetic,
+                          const double* params, const int32_t* flags, const double* step,
+                          const double* z, uint64_t seed, int64_t obs_first, double* stats,
+                          double* payoff_out) {
+  int rc = check_sizes(B, n_steps, n_obs, antithetic);
+  if (rc) return rc;
+  if (!params) return mfail(FDCN_EINVAL, "mc_barrier_batch: params is NULL");
+  if (!flags) return mfail(FDCN_EINVAL, "mc_barrier_batch: flags is NULL");
+  if (!step) return mfail(FDCN_EINVAL, "mc_barrier_batch: step is NULL");
+  if (!stats) return mfail(FDCN_EINVAL, "mc_barrier_batch: stats is NULL");
+  rc = check_contracts(B, params, flags);
+  if (rc) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return mfail(FDCN_ENODEV, "no HIP device visible");
+  hipStream_t stream;
+  rc = fdcn_internal::thread_stream(&stream);
+  if (rc) return rc;
+
+  // one stream-ordered block for every device array of the call
+  const size_t nb = (size_t)B;
+  const size_t bP = sizeof(double) * nb * FDCN_MC_NPARAM;
+  const size_t bF = sizeof(int32_t) * nb * FDCN_MC_NFLAG;
+  const size_t bS = sizeof(double) * nb * (size_t)n_steps * FDCN_MC_NSTEP;
+  const size_t bZ = z ? sizeof(double) * (size_t)n_obs * (size_t)n_steps : 0;
+  const size_t bO = sizeof(double) * nb * FDCN_MC_NSTAT;
+  const size_t bY = payoff_out ? sizeof(double) * nb * (size_t)n_obs : 0;
+  const size_t bW = sizeof(double) * 2 * (size_t)blocks_for(n_obs) * nb;
+  const size_t oP = 0;
+  const size_t oF = oP + align256(bP);
+  const size_t oS = oF + align256(bF);
+  const size_t oZ = oS + align256(bS);
+  const size_t oO = oZ + align256(bZ);
+  const size_t oY = oO + align256(bO);
+  const size_t oW = oY + align256(bY);
+  const size_t total = oW + align256(bW);
+  char* blk = nullptr;
+  if (hipMallocAsync((void**)&blk, total, stream) != hipSuccess)
+    return mfail(FDCN_ENOMEM, "mc_barrier_batch: hipMallocAsync failed");
+  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
+  hipError_t e = hipMemcpyAsync(blk + oP, params, bP, h2d, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(blk + oF, flags, bF, h2d, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(blk + oS, step, bS, h2d, stream);
+  if (e == hipSuccess && z) e = hipMemcpyAsync(blk + oZ, z, bZ, h2d, stream);
+  if (e != hipSuccess) rc = mfail(FDCN_EHIP, "mc_barrier_batch: H2D copy failed");
+  if (rc == FDCN_OK)
+    rc = launch(B, n_steps, n_obs, antithetic, (const double*)(blk + oP),
+                (const int32_t*)(blk + oF), (const double*)(blk + oS),
+                z ? (const double*)(blk + oZ) : nullptr, seed, obs_first, (double*)(blk + oO),
+                payoff_out ? (double*)(blk + oY) : nullptr, (double*)(blk + oW), stream);
+  if (rc == FDCN_OK) {
+    e = hipMemcpyAsync(stats, blk + oO, bO, d2h, stream);
+    if (e == hipSuccess && payoff_out) e = hipMemcpyAsync(payoff_out, blk + oY, bY, d2h, stream);
+    if (e != hipSuccess) rc = mfail(FDCN_EHIP, "mc_barrier_batch: D2H copy failed");
+  }
+  (void)hipFreeAsync(blk, stream);
+  e = hipStreamSynchronize(stream);
+  if (rc == FDCN_OK && e != hipSuccess)
+    rc = mfail(FDCN_EHIP, "mc_barrier_batch: kernel / copies failed");
+  return rc;
+}
+
+int fdcn_mc_normals(int64_t n_obs, int32_t n_steps, uint64_t seed, int32_t stream_id,
+                    int64_t obs_first, double* z) {
+  if (n_obs < 1) return mfail(FDCN_EINVAL, "mc_normals: n_obs must be >= 1");
+  if (n_steps < 1) return mfail(FDCN_EINVAL, "mc_normals: n_steps must be >= 1");
+  if (stream_id < 0) return mfail(FDCN_EINVAL, "mc_normals: stream id must be >= 0");
+  if (!z) return mfail(FDCN_EINVAL, "mc_normals: z is NULL");
+  const int64_t threads = n_obs * (((int64_t)n_steps + 1) / 2);
+  const int64_t grid = (threads + kThreads - 1) / kThreads;
+  if (n_obs > ((int64_t)1 << 40) || grid > 0x7fffffffLL)
+    return mfail(FDCN_EINVAL, "mc_normals: n_obs * n_steps is beyond one launch's grid");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return mfail(FDCN_ENODEV, "no HIP device visible");
+  hipStream_t stream;
+  int rc = fdcn_internal::thread_stream(&stream);
+  if (rc) return rc;
+  const size_t bytes = sizeof(double) * (size_t)n_obs * (size_t)n_steps;
+  double* dz = nullptr;
+  if (hipMallocAsync((void**)&dz, bytes, stream) != hipSuccess)
+    return mfail(FDCN_ENOMEM, "mc_normals: hipMallocAsync failed");
+  hipLaunchKernelGGL(mc_normals_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, stream, n_obs,
+                     n_steps, seed, (uint32_t)stream_id, obs_first, dz);
+  if (hipGetLastError() != hipSuccess) rc = mfail(FDCN_EHIP, "mc_normals: launch failed");
+  if (rc == FDCN_OK && hipMemcpyAsync(z, dz, bytes, hipMemcpyDeviceToHost, stream) != hipSuccess)
+    rc = mfail(FDCN_EHIP, "mc_normals: D2H copy failed");
+  (void)hipFreeAsync(dz, stream);
+  const hipError_t e = hipStreamSynchronize(stream);
+  if (rc == FDCN_OK && e != hipSuccess) rc = mfail(FDCN_EHIP, "mc_normals: kernel / copy failed");
+  return rc;
+}
+
+}  // extern "C"

@@ -45,11 +45,14 @@
 extern "C" {
 #endif
 
-/* 5: fdcn_session_host_buffer, the diagnostics of include/fdcn_diag.h for the
+/* 6: the Monte Carlo discrete-barrier entry points (fdcn_mc_barrier_batch,
+ * fdcn_mc_barrier_batch_dev, fdcn_mc_plan; fdcn_mc_normals in fdcn_diag.h)
+ * were added to the exported surface after 5.
+ * 5: fdcn_session_host_buffer, the diagnostics of include/fdcn_diag.h for the
  * spot-space kernels (fdcn_vc_force_variant / _variant_name / _forms) and the
  * fdcn_vc workspace contract (+16 doubles per scenario) changed the exported
  * surface after 4 */
-#define FDCN_ABI_VERSION 5
+#define FDCN_ABI_VERSION 6
 
 /* ---- per-scenario fp64 parameters: params[b*FDCN_NPARAM + k] ---------- */
 enum fdcn_param {
@@ -329,6 +332,100 @@ int fdcn_double_barrier_batch(int32_t B, int32_t m, const double* params,
                               const int32_t* flags, double* price);
 int fdcn_double_barrier_batch_dev(int32_t B, int32_t m, const double* params,
                                   const int32_t* flags, double* price, void* stream);
+
+/* ---- Monte Carlo discrete-barrier pricer (finite_difference_amd/csrc/fdcn_mc.hip)
+ * fdcn_mc_barrier_batch <- price_discrete_barrier_mc's path loop and estimator
+ *                          (mc_discrete_barrier_option.py:314-410).
+ * One launch prices B contracts that share n_steps, n_obs and `antithetic`;
+ * the host computes every curve quantity (event grid, carry per interval,
+ * discount factors, the barrier band).
+ *   params[B][FDCN_MC_NPARAM]        see enum fdcn_mc_param
+ *   flags [B][FDCN_MC_NFLAG]         see enum fdcn_mc_flag
+ *   step  [B][n_steps][FDCN_MC_NSTEP] see enum fdcn_mc_step
+ * Path, per step i (the reference's order):  s *= exp(drift + diff * z_i);
+ * the cash dividend s = max(s - D, floor) before the monitor check if
+ * DIV_FIRST, after it otherwise; on a monitor step the breach test
+ * s <= threshold (down kinds) / s >= threshold (up kinds).  At the end the
+ * vanilla payoff max(+-(s - strike), 0) * df_T: paid to untouched paths
+ * (knock-out), to touched paths (knock-in), to all (kind 0); a knocked-out
+ * path pays rebate * df_T, or rebate * DF_END of its first hit step with
+ * REBATE_AT_HIT.  An observation is f(Z), or 0.5 * (f(Z) + f(-Z)) with
+ * antithetic != 0; n_obs counts observations.
+ *
+ * Normals.  z != NULL: z [n_obs][n_steps], shared by all B contracts (the
+ * reference shares one stream per call); observation i reads row i.
+ * z == NULL: generated with Philox4x32-10.  This mapping is a contract:
+ *   counter = (o & 0xffffffff, o >> 32, j, stream id),  o = obs_first + i,
+ *   key     = (seed & 0xffffffff, seed >> 32),
+ *   x0..x3  = Philox4x32-10(counter, key)   (Random123: multipliers D2511F53,
+ *             CD9E8D57; key increments 9E3779B9, BB67AE85),
+ *   u1 = ((x0 >> 5) * 2^26 + (x1 >> 6) + 0.5) * 2^-53,  u2 likewise from x2, x3
+ *        (evaluated in fp64 in that order),
+ *   z[2j]   = sqrt(-2 ln u1) * cospi(2 u2),
+ *   z[2j+1] = sqrt(-2 ln u1) * sinpi(2 u2)   (dropped when 2j+1 == n_steps).
+ * Disjoint [obs_first, obs_first + n_obs) ranges of one (seed, stream id)
+ * continue one stream: ranks shard the paths of a contract, or a run resumes,
+ * and sum p / sum p^2 of the parts add up.
+ *
+ * Reduction.  Deterministic, no floating-point atomics: a workgroup owns a
+ * fixed chunk of observations (fdcn_mc_plan: a function of n_obs only), each
+ * thread adds its observations in index order, the workgroup reduces in a
+ * fixed tree, and a second kernel adds the per-workgroup partials in order.
+ * A contract's result depends on neither B nor its position in the batch.
+ *   stats [B][FDCN_MC_NSTAT] = price = sum p / n, stderr =
+ *                              sqrt(max(0, sum p^2 / n - price^2) / n),
+ *                              sum p, sum p^2
+ *   payoff_out [B][n_obs]      the observations (NULL: not written)
+ * Validation (before any device call; FDCN_EINVAL): B, n_steps, n_obs < 1;
+ * antithetic or a flag out of range; NULL params / flags / step / stats; and,
+ * host entry only, spot or strike <= 0, threshold <= 0 where KIND != 0. */
+#define FDCN_MC_NPARAM 6
+enum fdcn_mc_param {
+  FDCN_MC_P_SPOT = 0,
+  FDCN_MC_P_STRIKE,
+  FDCN_MC_P_DF_T,      /* discount factor to maturity                          */
+  FDCN_MC_P_THRESHOLD, /* level + band (down kinds) / level - band (up kinds)  */
+  FDCN_MC_P_REBATE,    /* cash amount paid to a knocked-out path               */
+  FDCN_MC_P_FLOOR      /* spot floor after a cash dividend                     */
+};
+#define FDCN_MC_NFLAG 5
+enum fdcn_mc_flag {
+  FDCN_MC_F_PUT = 0,       /* 0 call, 1 put                                      */
+  FDCN_MC_F_KIND,          /* 0 none, 1 down-out, 2 up-out, 3 down-in, 4 up-in   */
+  FDCN_MC_F_REBATE_AT_HIT, /* 1: the rebate is discounted from its hit date      */
+  FDCN_MC_F_DIV_FIRST,     /* 1: dividend_before_monitor                         */
+  FDCN_MC_F_STREAM         /* Philox stream id (>= 0), counter word 3            */
+};
+#define FDCN_MC_NSTEP 5
+enum fdcn_mc_step {
+  FDCN_MC_S_DRIFT = 0, /* (carry - sigma^2 / 2) * tau                           */
+  FDCN_MC_S_DIFF,      /* sigma * sqrt(tau)                                     */
+  FDCN_MC_S_DIV,       /* cash dividend at the step's end date (0: none)        */
+  FDCN_MC_S_MONITOR,   /* 1.0 if the end date is monitored, else 0.0            */
+  FDCN_MC_S_DF_END     /* discount factor at the end date (rebate at hit)       */
+};
+#define FDCN_MC_NSTAT 4
+/* Host pointers; copies in and out on the calling thread's stream (see
+ * "Threading" above) and waits for it. */
+int fdcn_mc_barrier_batch(int32_t B, int32_t n_steps, int64_t n_obs, int32_t antithetic,
+                          const double* params, const int32_t* flags, const double* step,
+                          const double* z, uint64_t seed, int64_t obs_first, double* stats,
+                          double* payoff_out);
+/* Device pointers, asynchronous on `stream`, no host sync.  `workspace` is
+ * device scratch of at least B * ws_bytes_per_contract (fdcn_mc_plan) bytes
+ * -- a smaller workspace_bytes is FDCN_EINVAL -- or NULL: allocated
+ * stream-ordered for the call.  The flags are device memory, so their range
+ * is not checked here: the kernel treats a KIND outside 0..4 as 0. */
+int fdcn_mc_barrier_batch_dev(int32_t B, int32_t n_steps, int64_t n_obs, int32_t antithetic,
+                              const double* params, const int32_t* flags, const double* step,
+                              const double* z, uint64_t seed, int64_t obs_first, double* stats,
+                              double* payoff_out, double* workspace, int64_t workspace_bytes,
+                              void* stream);
+/* Geometry of a launch of n_obs observations per contract: workgroups per
+ * contract, observations per workgroup, workspace bytes per contract.  Any
+ * output pointer may be NULL.  Host only. */
+int fdcn_mc_plan(int64_t n_obs, int32_t* blocks_per_contract, int32_t* obs_per_block,
+                 int64_t* ws_bytes_per_contract);
 
 /* ---- host-side plan helpers (no device) -------------------------------- */
 /* Uniform log grid of the pricers' _build_log_grid

@@ -55,6 +55,13 @@ int fdcn_vc_variant_name(int32_t B, int32_t n_nodes, char* buf, int32_t len);
 int fdcn_vc_forms(int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
                   const double* diag, int32_t* form);
 
+/* The normals the Monte Carlo path kernel generates for (seed, stream id)
+ * and observations obs_first .. obs_first + n_obs - 1 (the Philox mapping of
+ * include/fdcn.h, the same device function), into z [n_obs][n_steps] (host
+ * memory).  Lets a test restate the mapping and compare. */
+int fdcn_mc_normals(int64_t n_obs, int32_t n_steps, uint64_t seed, int32_t stream_id,
+                    int64_t obs_first, double* z);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,6 +2,11 @@
 """Instruction mix of a kernel's time loop, from a hipcc --save-temps .s file.
 
 Usage: python tools/isa_stats.py FILE.s IT W NPT [ZG]
+       python tools/isa_stats.py FILE.s --kernel SUBSTRING
+
+The second form takes any kernel whose mangled name contains SUBSTRING (the
+Monte Carlo path kernel: mc_path_kernelILb1ELb1E) and also prints the fp64
+operations of its longest loop, an FMA counted as two.
 
 Finds the kernel fdcn_march<IT,W,NPT,ZG>, takes the instructions between the
 longest backward branch's target and the branch (the time loop), and counts
@@ -14,10 +19,14 @@ import sys
 from collections import Counter
 
 
-def kernel_lines(path, it, w, npt, zg):
+def kernel_lines(path, it, w, npt, zg, substring=None):
     name = f"_ZN12_GLOBAL__N_110fdcn_marchILi{it}ELi{w}ELi{npt}ELi{zg}EEEvNS_5KArgsE:"
     lines = open(path).read().splitlines()
-    start = next(i for i, l in enumerate(lines) if l.startswith(name))
+    if substring is None:
+        start = next(i for i, l in enumerate(lines) if l.startswith(name))
+    else:
+        start = next(i for i, l in enumerate(lines)
+                     if re.match(r"^_Z\w+:", l) and substring in l)
     end = next(i for i in range(start + 1, len(lines)) if lines[i].strip().startswith("s_endpgm"))
     meta = []
     for l in lines[end:end + 80]:
@@ -53,9 +62,15 @@ def classify(op):
 
 
 def main():
-    path, it, w, npt = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
-    zg = int(sys.argv[5]) if len(sys.argv) > 5 else 0
-    ks, meta = kernel_lines(path, it, w, npt, zg)
+    path = sys.argv[1]
+    generic = sys.argv[2] == "--kernel"
+    if generic:
+        it = w = npt = zg = 0
+        ks, meta = kernel_lines(path, 0, 0, 0, 0, substring=sys.argv[3])
+    else:
+        it, w, npt = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
+        zg = int(sys.argv[5]) if len(sys.argv) > 5 else 0
+        ks, meta = kernel_lines(path, it, w, npt, zg)
     labels = {l.split(":")[0]: i for i, l in enumerate(ks) if re.match(r"^\.LBB\d+_\d+:", l)}
     best = None
     for i, l in enumerate(ks):
@@ -66,16 +81,24 @@ def main():
                 best = (span, labels[m.group(1)], i)
     _, a, b = best
     cnt = Counter()
+    flops = 0
     for l in ks[a:b + 1]:
         s = l.strip()
         if not s or s.startswith((";", ".")) or s.endswith(":"):
             continue
-        cnt[classify(s.split()[0])] += 1
+        op = s.split()[0]
+        cnt[classify(op)] += 1
+        if classify(op) == "valu_f64" and not op.startswith(("v_cmp", "v_cvt")):
+            flops += 2 if "fma" in op else 1
     total = sum(cnt.values())
-    print(f"fdcn_march<{it},{w},{npt},{zg}> loop: {total} instructions (static)")
+    title = ks[0].rstrip(":") if generic else f"fdcn_march<{it},{w},{npt},{zg}>"
+    print(f"{title} loop: {total} instructions (static)")
     for k, v in cnt.most_common():
         print(f"  {k:14s} {v:6d}")
-    print("  f64 VALU per node:", round(cnt["valu_f64"] / npt, 2))
+    if generic:
+        print("  f64 operations in the loop (FMA = 2):", flops)
+    else:
+        print("  f64 VALU per node:", round(cnt["valu_f64"] / npt, 2))
     for l in meta:
         print("  " + l)
 
