@@ -30,7 +30,7 @@ P_HI_C0, P_HI_E0, P_HI_C1, P_HI_E1 = 9, 10, 11, 12
 NPARAM = 13
 I_LO_FORM, I_HI_FORM, I_KO_LO, I_KO_HI, I_MON_START, I_MON_COUNT, I_TAU_MODE = range(7)
 NIPARAM = 7
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 EXPORTED = ("fdcn_cn_batch", "fdcn_it_batch", "fdcn_cn_batch_dev", "fdcn_it_batch_dev",
             "fdcn_plan", "fdcn_sm_extent", "fdcn_log_grid", "fdcn_dividend_jump",
@@ -44,7 +44,8 @@ EXPORTED = ("fdcn_cn_batch", "fdcn_it_batch", "fdcn_cn_batch_dev", "fdcn_it_batc
             "fdcn_session_dividend_jump", "fdcn_session_greeks", "fdcn_session_fetch",
             "fdcn_vc_batch", "fdcn_vc_batch_dev", "fdcn_vc_plan", "fdcn_barrier_plan",
             "fdcn_vmath", "fdcn_american_plan", "fdcn_device_ordinals",
-            "fdcn_mc_barrier_batch", "fdcn_mc_barrier_batch_dev", "fdcn_mc_plan")
+            "fdcn_mc_barrier_batch", "fdcn_mc_barrier_batch_dev", "fdcn_mc_plan",
+            "fdcn_mc_bgk_batch", "fdcn_mc_bgk_batch_dev", "fdcn_mc_bgk_plan")
 # include/fdcn_diag.h: test / tuning entry points, not the product boundary
 DIAG_EXPORTED = ("fdcn_force_variant", "fdcn_forced_variant", "fdcn_variant_name",
                  "fdcn_vc_force_variant", "fdcn_vc_variant_name", "fdcn_vc_forms",
@@ -59,6 +60,12 @@ MC_P_SPOT, MC_P_STRIKE, MC_P_DF_T, MC_P_THRESHOLD, MC_P_REBATE, MC_P_FLOOR = ran
 MC_F_PUT, MC_F_KIND, MC_F_REBATE_AT_HIT, MC_F_DIV_FIRST, MC_F_STREAM = range(5)
 MC_S_DRIFT, MC_S_DIFF, MC_S_DIV, MC_S_MONITOR, MC_S_DF_END = range(5)
 MC_KIND = {"none": 0, "down-and-out": 1, "up-and-out": 2, "down-and-in": 3, "up-and-in": 4}
+# BGK pricer's Monte Carlo paths (enum fdcn_bgk_param / _flag / _step)
+BGK_MAX_G, BGK_NPARAM, BGK_NFLAG, BGK_NSTEP, BGK_NSTAT = 8, 7, 4, 4, 4
+(BGK_P_LOG_SPOT, BGK_P_STRIKE, BGK_P_UPPER, BGK_P_LOWER, BGK_P_EPS_BARRIER, BGK_P_EPS_PAYOFF,
+ BGK_P_REBATE) = range(7)
+BGK_F_PUT, BGK_F_SIDES, BGK_F_REBATE_MODE, BGK_F_STREAM = range(4)
+BGK_S_DRIFT, BGK_S_DIFF, BGK_S_MONITOR, BGK_S_DF_END = range(4)
 
 
 class FdcnError(RuntimeError):
@@ -252,6 +259,14 @@ def lib() -> ctypes.CDLL:
                                                     ctypes.c_uint64, _I64, _V, _V, _V, _I64, _V]
             L.fdcn_mc_plan.restype = _I
             L.fdcn_mc_plan.argtypes = [_I64, _PI, _PI, ctypes.POINTER(ctypes.c_int64)]
+            L.fdcn_mc_bgk_batch.restype = _I
+            L.fdcn_mc_bgk_batch.argtypes = [_I, _I, _I, _I64, _I, _V, _V, _V, _V, ctypes.c_uint64,
+                                            _I64, _V, _V]
+            L.fdcn_mc_bgk_batch_dev.restype = _I
+            L.fdcn_mc_bgk_batch_dev.argtypes = [_I, _I, _I, _I64, _I, _V, _V, _V, _V,
+                                                ctypes.c_uint64, _I64, _V, _V, _V, _I64, _V]
+            L.fdcn_mc_bgk_plan.restype = _I
+            L.fdcn_mc_bgk_plan.argtypes = [_I64, _I, _PI, _PI, ctypes.POINTER(ctypes.c_int64)]
             L.fdcn_mc_normals.restype = _I
             L.fdcn_mc_normals.argtypes = [_I64, _I, ctypes.c_uint64, _I, _I64, _V]
             _lib = L
@@ -687,3 +702,59 @@ def mc_normals(n_obs: int, n_steps: int, seed: int, stream_id: int = 0,
     _check(lib().fdcn_mc_normals(int(n_obs), int(n_steps), int(seed) & (2 ** 64 - 1),
                                  int(stream_id), int(obs_first), z.ctypes.data))
     return z
+
+
+def mc_bgk_plan(n_obs: int, G: int = 1) -> dict:
+    """Geometry of a BGK path launch of n_obs observations per trade at group
+    size G (fdcn_mc_bgk_plan; host only): workgroups per trade, observations
+    per workgroup, workspace bytes per trade."""
+    nb, per = ctypes.c_int32(), ctypes.c_int32()
+    ws = ctypes.c_int64()
+    _check(lib().fdcn_mc_bgk_plan(int(n_obs), int(G), ctypes.byref(nb), ctypes.byref(per),
+                                  ctypes.byref(ws)))
+    return dict(blocks_per_trade=nb.value, obs_per_block=per.value, ws_bytes_per_trade=ws.value)
+
+
+def mc_bgk_batch(params, flags, step, n_obs: int, antithetic: bool, *, z=None, seed: int = 0,
+                 obs_first: int = 0, want_payoffs: bool = False):
+    """fdcn_mc_bgk_batch on host arrays -> stats [B, G, BGK_NSTAT] (sum x,
+    sum x^2, sum rebate_pv, sum (1 - alive) over the n_sim paths), or (stats,
+    payoffs [B, G, 2, n_sim]) with want_payoffs.  params [B, G, BGK_NPARAM],
+    flags [B, BGK_NFLAG], step [B, G, n_steps, BGK_NSTEP]; z [n_obs, n_steps]
+    supplies the normals, None generates them on the device from `seed`, the
+    trades' stream ids and `obs_first`."""
+    require_device()
+    P = _f64(params)
+    F = _i32(flags)
+    S = _f64(step)
+    if (P.ndim != 3 or P.shape[2] != BGK_NPARAM or F.shape != (P.shape[0], BGK_NFLAG)
+            or S.ndim != 4 or S.shape[:2] != P.shape[:2] or S.shape[3] != BGK_NSTEP):
+        raise ValueError("mc_bgk_batch: params [B, G, 7], flags [B, 4], step [B, G, n_steps, 4]")
+    B, G = P.shape[:2]
+    n_steps = S.shape[2]
+    n_sim = int(n_obs) * (2 if antithetic else 1)
+    Z = None
+    if z is not None:
+        Z = _f64(z)
+        if Z.shape != (int(n_obs), n_steps):
+            raise ValueError(f"mc_bgk_batch: z must be [n_obs, n_steps] = {(n_obs, n_steps)}")
+    stats = np.empty((B, G, BGK_NSTAT), dtype=np.float64)
+    pay = np.empty((B, G, 2, n_sim), dtype=np.float64) if want_payoffs else None
+    _check(lib().fdcn_mc_bgk_batch(
+        B, G, n_steps, int(n_obs), 1 if antithetic else 0, P.ctypes.data, F.ctypes.data,
+        S.ctypes.data, Z.ctypes.data if Z is not None else None, int(seed) & (2 ** 64 - 1),
+        int(obs_first), stats.ctypes.data, pay.ctypes.data if want_payoffs else None))
+    return (stats, pay) if want_payoffs else stats
+
+
+def mc_bgk_batch_dev(B: int, G: int, n_steps: int, n_obs: int, antithetic: bool, params_ptr: int,
+                     flags_ptr: int, step_ptr: int, z_ptr: Optional[int], seed: int,
+                     obs_first: int, stats_ptr: int, payoff_ptr: Optional[int],
+                     workspace_ptr: Optional[int], workspace_bytes: int,
+                     stream_ptr: Optional[int]) -> None:
+    """fdcn_mc_bgk_batch_dev: every array already on the device; asynchronous
+    on `stream_ptr`."""
+    _check(lib().fdcn_mc_bgk_batch_dev(
+        int(B), int(G), int(n_steps), int(n_obs), 1 if antithetic else 0, params_ptr, flags_ptr,
+        step_ptr, z_ptr, int(seed) & (2 ** 64 - 1), int(obs_first), stats_ptr, payoff_ptr,
+        workspace_ptr, int(workspace_bytes), stream_ptr))

@@ -45,14 +45,16 @@
 extern "C" {
 #endif
 
-/* 6: the Monte Carlo discrete-barrier entry points (fdcn_mc_barrier_batch,
+/* 7: the BGK barrier pricer's Monte Carlo entry points (fdcn_mc_bgk_batch,
+ * fdcn_mc_bgk_batch_dev, fdcn_mc_bgk_plan) were added after 6.
+ * 6: the Monte Carlo discrete-barrier entry points (fdcn_mc_barrier_batch,
  * fdcn_mc_barrier_batch_dev, fdcn_mc_plan; fdcn_mc_normals in fdcn_diag.h)
  * were added to the exported surface after 5.
  * 5: fdcn_session_host_buffer, the diagnostics of include/fdcn_diag.h for the
  * spot-space kernels (fdcn_vc_force_variant / _variant_name / _forms) and the
  * fdcn_vc workspace contract (+16 doubles per scenario) changed the exported
  * surface after 4 */
-#define FDCN_ABI_VERSION 6
+#define FDCN_ABI_VERSION 7
 
 /* ---- per-scenario fp64 parameters: params[b*FDCN_NPARAM + k] ---------- */
 enum fdcn_param {
@@ -426,6 +428,101 @@ int fdcn_mc_barrier_batch_dev(int32_t B, int32_t n_steps, int64_t n_obs, int32_t
  * output pointer may be NULL.  Host only. */
 int fdcn_mc_plan(int64_t n_obs, int32_t* blocks_per_contract, int32_t* obs_per_block,
                  int64_t* ws_bytes_per_contract);
+
+/* ---- Monte Carlo paths of the BGK barrier pricer (csrc/fdcn_mc_bgk.hip) ----
+ * fdcn_mc_bgk_batch <- DiscreteBarrierBGKPricer._mc_out_price's path functional
+ *                      (discrete_barrier_bgk.py:770-878).
+ * One launch prices B trades x G scenarios (1 <= G <= FDCN_BGK_MAX_G) that
+ * share n_steps, n_obs, `antithetic` and G.  The G scenarios of a trade (the
+ * bumped re-pricings of its Greeks) share the trade's flags and its normals:
+ * an observation's normals are drawn once and every scenario, and both signs,
+ * walk them.
+ *   params[B][G][FDCN_BGK_NPARAM]          see enum fdcn_bgk_param
+ *   flags [B][FDCN_BGK_NFLAG]              see enum fdcn_bgk_flag
+ *   step  [B][G][n_steps][FDCN_BGK_NSTEP]  see enum fdcn_bgk_step
+ * Path (every operation rounded separately, in this order).  Per step k:
+ * c += drift_k + diff_k * z_k (the mirrored path: drift_k - diff_k * z_k).
+ * On a monitored step S = exp(log_spot + c) and
+ *   event = max(max(0, up(S)), down(S)) over the active sides, where for a
+ *   barrier epsilon e > 0   up = 0 if S < Hu - e, 1 if S > Hu + e, else
+ *   0.5 + (S - Hu) / (2 e);  down = 1 if S < Hd - e, 0 if S > Hd + e, else
+ *   0.5 + (Hd - S) / (2 e);  and for e = 0  up = [S >= Hu], down = [S <= Hd];
+ *   rebate mode 2, e > 0:  newly = max(0, event - [rebate_pv > 0]),
+ *                          rebate_pv += (newly * R) * DF_END_k;
+ *   rebate mode 2, e = 0:  the first hit sets rebate_pv = R * DF_END_k;
+ *   breached += event.
+ * At the end S_T = exp(log_spot + c), alive = clip(1 - breached, 0, 1),
+ * d = S_T - K (call) or K - S_T (put), intrinsic = max(d, 0) for a payoff
+ * epsilon p = 0, else 0 if d < -p, d if d > p, else
+ * (0.5 d^2 + p d + 0.5 p^2) / (2 p);  x = alive * intrinsic, plus
+ * R * (1 - alive) in rebate mode 1.
+ * Paths: n_sim = n_obs * (1 + antithetic); path i is +z of observation i,
+ * path n_obs + i is -z.  Normals: z [n_obs][n_steps] shared by the launch, or
+ * NULL: the Philox mapping of fdcn_mc_barrier_batch above (counter = (o low,
+ * o high, pair, stream id), o = obs_first + i; key = seed), so disjoint
+ * obs_first ranges continue one stream and the sums of the parts add.
+ *   stats [B][G][FDCN_BGK_NSTAT] = raw sums over the n_sim paths: sum x,
+ *                                  sum x^2, sum rebate_pv, sum (1 - alive)
+ *   payoff_out [B][G][2][n_sim]    x, then rebate_pv (NULL: not written)
+ * The caller composes price and standard error (the pricer: DF_T * mean x +
+ * mean rebate_pv; sqrt((sum x^2 - (sum x)^2 / n) / (n - 1)) * DF_T / sqrt n).
+ * Reduction: as fdcn_mc_barrier_batch -- no floating-point atomics, a fixed
+ * chunk (fdcn_mc_bgk_plan), fixed tree, partials added in block order.  A
+ * scenario's sums are bit-identical whatever G, its slot, B, or the trade's
+ * position in the batch.
+ * Validation (before any device call; FDCN_EINVAL): B, n_steps, n_obs < 1; G
+ * outside 1..8; antithetic out of range; NULL params / flags / step / stats;
+ * and, host entry only: put, sides (0..3), rebate mode (0..2) or stream id out
+ * of range; a non-finite log-spot; strike <= 0; a negative epsilon; a level
+ * <= 0 on an active side. */
+#define FDCN_BGK_MAX_G 8
+#define FDCN_BGK_NPARAM 7
+enum fdcn_bgk_param {
+  FDCN_BGK_P_LOG_SPOT = 0, /* ln(spot), computed by the caller                  */
+  FDCN_BGK_P_STRIKE,
+  FDCN_BGK_P_UPPER,        /* upper level Hu (read if sides bit 0)               */
+  FDCN_BGK_P_LOWER,        /* lower level Hd (read if sides bit 1)               */
+  FDCN_BGK_P_EPS_BARRIER,  /* half-width of the smoothed barrier test; 0: exact  */
+  FDCN_BGK_P_EPS_PAYOFF,   /* half-width of the smoothed payoff; 0: exact        */
+  FDCN_BGK_P_REBATE        /* cash rebate R                                      */
+};
+#define FDCN_BGK_NFLAG 4
+enum fdcn_bgk_flag {
+  FDCN_BGK_F_PUT = 0,      /* 0 call, 1 put                                      */
+  FDCN_BGK_F_SIDES,        /* bit 0 upper active, bit 1 lower active, 0 vanilla  */
+  FDCN_BGK_F_REBATE_MODE,  /* 0 none, 1 at expiry, 2 at hit                      */
+  FDCN_BGK_F_STREAM        /* Philox stream id (>= 0), counter word 3            */
+};
+#define FDCN_BGK_NSTEP 4
+enum fdcn_bgk_step {
+  FDCN_BGK_S_DRIFT = 0, /* (mu - sigma^2 / 2) * dt                               */
+  FDCN_BGK_S_DIFF,      /* sigma * sqrt(dt)                                      */
+  FDCN_BGK_S_MONITOR,   /* 1.0 if the step's end is monitored, else 0.0; the same
+                           for the G scenarios of a trade                        */
+  FDCN_BGK_S_DF_END     /* discount factor at the step's end (rebate at hit)     */
+};
+#define FDCN_BGK_NSTAT 4
+/* Host pointers; copies in and out on the calling thread's stream and waits. */
+int fdcn_mc_bgk_batch(int32_t B, int32_t G, int32_t n_steps, int64_t n_obs, int32_t antithetic,
+                      const double* params, const int32_t* flags, const double* step,
+                      const double* z, uint64_t seed, int64_t obs_first, double* stats,
+                      double* payoff_out);
+/* Device pointers, asynchronous on `stream`, no host sync.  `workspace` is
+ * device scratch of at least B * ws_bytes_per_trade (fdcn_mc_bgk_plan) bytes
+ * -- a smaller workspace_bytes is FDCN_EINVAL -- or NULL: allocated
+ * stream-ordered for the call.  The flags are device memory, so their range is
+ * not checked here: the kernel masks sides to two bits and treats a rebate
+ * mode outside 0..2 as 0. */
+int fdcn_mc_bgk_batch_dev(int32_t B, int32_t G, int32_t n_steps, int64_t n_obs,
+                          int32_t antithetic, const double* params, const int32_t* flags,
+                          const double* step, const double* z, uint64_t seed, int64_t obs_first,
+                          double* stats, double* payoff_out, double* workspace,
+                          int64_t workspace_bytes, void* stream);
+/* Geometry of a launch of n_obs observations per trade at group size G:
+ * workgroups per trade, observations per workgroup (a constant), workspace
+ * bytes per trade.  Any output pointer may be NULL.  Host only. */
+int fdcn_mc_bgk_plan(int64_t n_obs, int32_t G, int32_t* blocks_per_trade, int32_t* obs_per_block,
+                     int64_t* ws_bytes_per_trade);
 
 /* ---- host-side plan helpers (no device) -------------------------------- */
 /* Uniform log grid of the pricers' _build_log_grid
