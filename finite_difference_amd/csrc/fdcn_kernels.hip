@@ -1068,8 +1068,9 @@ fdcn_march(KArgs A) {
   constexpr bool kTPST = kTPS && NPT <= 16;
   static_assert(!kTP || (M >= 2 && !kPair), "two-pass: one scenario per wave, M >= 2");
   static_assert(!kTPS || (kSplit && S == 1), "split two-pass: the split form, S = 1");
-  // DPP broadcast table registers per table (16 entries each)
-  constexpr int kTabRegs = kTPS ? (M + 15) / 16 : 1;
+  // DPP broadcast table registers per table (16 entries each): every
+  // two-pass variant (IT: M = NPT / S entries, one to three registers)
+  constexpr int kTabRegs = kTP ? (M + 15) / 16 : 1;
   // doubles per phase: P', G, the lz Sherman-Morrison rows and a zero row
   // (the lanes past the table read it)
   const int kTPh = kTP ? 2 * M + (lz + 1) * 2 * S : 0;
@@ -1972,27 +1973,28 @@ fdcn_march(KArgs A) {
     return kTP ? lds_addr(ztab + tb_ * kTPh + 2 * M + (t < lz ? t : lz) * 2 * S) : 0u;
   };
   unsigned tp_ta = tp_tab_addr(1), tp_za = tp_row_addr(1);
-  // kTPS: this phase's P' and G as DPP broadcast sources (fmac_bcast), lane
+  // kTP: this phase's P' and G as DPP broadcast sources (fmac_bcast), lane
   // l holding entry l mod 16 (more than 16 slots: register r holds entries
-  // 16 r .. 16 r + 15), times the phase's update scale s
+  // 16 r .. 16 r + 15); kTPS: times the phase's update scale s, IT: as
+  // tabulated (the LDS copies are then read only here)
   double tabP[kTabRegs], tabG[kTabRegs];
 #pragma unroll
   for (int r = 0; r < kTabRegs; ++r) tabP[r] = tabG[r] = 0.0;
   auto tp_load_bcast = [&](int tb_, double sc) __attribute__((always_inline)) {
-    if constexpr (kTPS) {
+    if constexpr (kTP) {
       const double* tb = ztab + tb_ * kTPh;
 #pragma unroll
       for (int r = 0; r < kTabRegs; ++r) {
         const int e = 16 * r + (lane & 15);
         const int sl = e < M ? e : 0;
-        tabP[r] = sc * tb[sl];
-        tabG[r] = sc * tb[M + sl];
+        tabP[r] = IT ? tb[sl] : sc * tb[sl];
+        tabG[r] = IT ? tb[M + sl] : sc * tb[M + sl];
       }
     }
   };
   unsigned tp_pa = (kTP && kPhiLds) ? lds_addr(phit + t) : 0u;
-  // kTPS tables: times the update scale s, or unscaled for kTPST
-  auto tab_scale = [&]() __attribute__((always_inline)) { return kTPST ? 1.0 : ph.s; };
+  // kTPS tables: times the update scale s, or unscaled for kTPST (and IT)
+  auto tab_scale = [&]() __attribute__((always_inline)) { return (kTPST || IT) ? 1.0 : ph.s; };
   (void)tp_ta;
   (void)tp_za;
   (void)tp_pa;
@@ -2123,6 +2125,11 @@ fdcn_march(KArgs A) {
       for (int k = 0; k < NPT; ++k) V[k] += QS[k];
       V[0] = fma(e_first, lo_new, V[0]);            // + blo on the first lane
       V[NPT - 1] = fma(e_last, hi_new, V[NPT - 1]);  // + bhi on the last (never short)
+      // (kept as a select, two v_cndmask_b32: a multiply by a per-lane 0/1
+      // would be one instruction, but the phantom slot passes the lane's last
+      // real values through the solve and the update, so a scenario whose
+      // values overflow or start non-finite puts Inf/NaN there and 0 * Inf
+      // would feed a NaN where the reference's rhs has none)
       if (shrt) V[NPT - 1] = 0.0;                   // the phantom slot's rhs
     } else if constexpr (kSplit) {
       // theta form of the reference step A x = B V (+ Dirichlet terms,
@@ -2274,62 +2281,72 @@ fdcn_march(KArgs A) {
     } else if constexpr (kTP) {
       // ---- 2. two-pass solve; Sherman-Morrison folded into the carries ----
       solve_tp(ph);
-      tp_ta = hide_addr(tp_ta);  // this phase's tables
       tp_za = hide_addr(tp_za);
+      tp_pa = hide_addr(tp_pa);
+      // node of the u-th entry of group q: slot (q+u)/S of sub-chain (q+u)%S
+#define FDCN_TP_K(q, u) ((((q) + (u)) % S) * M + ((q) + (u)) / S)
+      // The payoff one four-node group ahead of its use: the tables come by
+      // DPP (below), so the payoff is the update's only LDS traffic, and the
+      // wait in front of a group's W/max/Q' block covers no load younger
+      // than the group's 8 FMAs.  The first group's loads go out before the
+      // Sherman-Morrison fold.  The compiler counts the loads still in flight
+      // itself (LDS returns in order: s_waitcnt lgkmcnt(2)); the
+      // sched_barriers hold the loads where they are written.  Two groups
+      // ahead measured 0.4 % slower at the same register count (DESIGN
+      // section 3).
+      constexpr int kGroups = NPT / 4;
+      constexpr int kPkAhead = kGroups < 1 ? kGroups : 1;
+      double pk[kGroups > 0 ? kGroups : 1][4];
+      (void)pk;
+      if constexpr (NPT % 4 == 0) {
+#pragma unroll
+        for (int g = 0; g < kPkAhead; ++g)
+#pragma unroll
+          for (int u = 0; u < 4; ++u) pk[g][u] = lds_ld(tp_pa, FDCN_TP_K(4 * g, u) * L);
+        __builtin_amdgcn_sched_barrier(0);
+      }
 #pragma unroll
       for (int j = 0; j < S; ++j) sm_fold(lds_ld(tp_za, j), lds_ld(tp_za, S + j), CC[j], DD[j]);
       DD[S - 1] = k2 * fma(CC[S - 1], k1, DD[S - 1]);  // short lanes (see setup_scan)
       // ---- 3. x = Wr + C P'_i + D G_i and the step's update ---------------
-      // nodes in (slot i, sub-chain j) order, four at a time: a slot's two
-      // table values (LDS broadcasts) serve all S sub-chains
+      // nodes in (slot i, sub-chain j) order, four at a time; slot i's P'_i
+      // and G_i are broadcast from the table registers straight into the FMAs
+      // (fmac_bcast: no LDS read, no register for the value, no wait), in
+      // the order C P' first, then D G
       __builtin_amdgcn_s_setprio(1);
       const double cq = (m + 1 < A.n_ranna) ? 1.0 : 2.0;  // 1/theta of the next step
-      tp_pa = hide_addr(tp_pa);
-      // node of the u-th entry of group q: slot (q+u)/S of sub-chain (q+u)%S
-#define FDCN_TP_K(u) ((((q) + (u)) % S) * M + ((q) + (u)) / S)
       if constexpr (NPT % 4 != 0) {
         // two-node chunks (the smallest grids): node by node, one sub-chain
         static_assert(S == 1, "chunks of fewer than 4 nodes run one sub-chain");
 #pragma unroll
         for (int k = 0; k < NPT; ++k) {
-          V[k] = fma(DD[0], lds_ld(tp_ta, M + k), fma(CC[0], lds_ld(tp_ta, k), V[k]));
+          fmac_bcast(V[k], tabP[k / 16], CC[0], k % 16);
+          fmac_bcast(V[k], tabG[k / 16], DD[0], k % 16);
           const double w = fma(ph.inv_r, V[k], -QS[k]);
           V[k] = fmax(lds_ld(tp_pa, k * L), w);
           QS[k] = fma(cq, V[k], -w);
         }
       } else {
-      // the tables one group ahead of their use (LDS latency under the
-      // previous group's arithmetic)
-      double tpn[4], tgn[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        tpn[u] = lds_ld(tp_ta, u / S);
-        tgn[u] = lds_ld(tp_ta, M + u / S);
-      }
 #pragma unroll
       for (int q = 0; q < NPT; q += 4) {
-        double tpc[4], tgc[4];
+        constexpr int kAheadQ = 4 * kPkAhead;
+        if (q + kAheadQ < NPT) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            pk[q / 4 + kPkAhead][u] = lds_ld(tp_pa, FDCN_TP_K(q + kAheadQ, u) * L);
+        }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          tpc[u] = tpn[u];
-          tgc[u] = tgn[u];
-        }
-        if (q + 4 < NPT) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            tpn[u] = lds_ld(tp_ta, (q + 4 + u) / S);
-            tgn[u] = lds_ld(tp_ta, M + (q + 4 + u) / S);
-          }
+          const int i = (q + u) / S;
+          fmac_bcast(V[FDCN_TP_K(q, u)], tabP[i / 16], CC[(q + u) % S], i % 16);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          const int j = (q + u) % S;
-          V[FDCN_TP_K(u)] = fma(DD[j], tgc[u], fma(CC[j], tpc[u], V[FDCN_TP_K(u)]));
+          const int i = (q + u) / S;
+          fmac_bcast(V[FDCN_TP_K(q, u)], tabG[i / 16], DD[(q + u) % S], i % 16);
         }
         // the Ikonen-Toivanen update (W, V', Q'; see the re-run form below)
-        double pk[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) pk[u] = lds_ld(tp_pa, FDCN_TP_K(u) * L);
         asm volatile(
             "v_fma_f64 %4, %12, %0, -%4\n\t"
             "v_fma_f64 %5, %12, %1, -%5\n\t"
@@ -2343,10 +2360,11 @@ fdcn_march(KArgs A) {
             "v_fma_f64 %5, %13, %1, -%5\n\t"
             "v_fma_f64 %6, %13, %2, -%6\n\t"
             "v_fma_f64 %7, %13, %3, -%7"
-            : "+v"(V[FDCN_TP_K(0)]), "+v"(V[FDCN_TP_K(1)]), "+v"(V[FDCN_TP_K(2)]),
-              "+v"(V[FDCN_TP_K(3)]), "+v"(QS[FDCN_TP_K(0)]), "+v"(QS[FDCN_TP_K(1)]),
-              "+v"(QS[FDCN_TP_K(2)]), "+v"(QS[FDCN_TP_K(3)])
-            : "v"(pk[0]), "v"(pk[1]), "v"(pk[2]), "v"(pk[3]), "s"(ph.inv_r), "s"(cq));
+            : "+v"(V[FDCN_TP_K(q, 0)]), "+v"(V[FDCN_TP_K(q, 1)]), "+v"(V[FDCN_TP_K(q, 2)]),
+              "+v"(V[FDCN_TP_K(q, 3)]), "+v"(QS[FDCN_TP_K(q, 0)]), "+v"(QS[FDCN_TP_K(q, 1)]),
+              "+v"(QS[FDCN_TP_K(q, 2)]), "+v"(QS[FDCN_TP_K(q, 3)])
+            : "v"(pk[q / 4][0]), "v"(pk[q / 4][1]), "v"(pk[q / 4][2]), "v"(pk[q / 4][3]),
+              "s"(ph.inv_r), "s"(cq));
       }
       }  // NPT % 4 == 0
 #undef FDCN_TP_K
