@@ -12,3 +12,4 @@ from .engine import Engine, Solve, Boundary, default_engine  # noqa: F401
 from .mc_barrier import (NacaCurve, BarrierSpec, RebateSpec, MCConfig,  # noqa: F401
                          price_discrete_barrier_mc, mc_barrier_batch, merge_mc_stats)
 from .bgk_barrier import DiscreteBarrierBGKPricer, bgk_price_batch  # noqa: F401
+from .american_barrier import AmericanBarrierFDMPricer  # noqa: F401

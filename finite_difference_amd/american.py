@@ -21,6 +21,11 @@ segments (natural cubic spline, fd_american_equity.py:479-553, 732-772) runs
 on the device, and the Richardson / vega / theta epilogue (:925-1068) too;
 six numbers per trade come back.  With another engine (the CPU oracle in the
 tests) the host-side jump and epilogue below are used.
+
+What happens between two segments is an ordered list of events per grid job
+(``_job_events``): the dividend jump here, and the knock-out of a monitoring
+date in american_barrier.py's subclass; vanilla and barrier trades march
+together in ``greeks_many`` / ``prefetch_many``.
 """
 from __future__ import annotations
 
@@ -380,12 +385,14 @@ class AmericanFDMPricer:
         s = self._segment_solve(v_init, tau_start, tau_end, n_steps, restart_rannacher)
         return self._engine().run([s])[0].tolist()
 
-    def _segments(self, n_time: int):
+    def _segments_over(self, taus: Sequence[float], n_time: int):
+        """(pts, steps) of a march cut at the ascending event times `taus`
+        (the rule of fd_american_equity.py:778-843): max(1, round(len / base_dt)) steps
+        per segment, the last takes the remainder, at least 1."""
         total_tau = self.time_to_expiry
-        divs = self._div_times_tau()
         base_n = int(n_time)
         base_dt = total_tau / float(base_n)
-        pts = [0.0] + [t for t, _ in divs] + [total_tau]
+        pts = [0.0] + list(taus) + [total_tau]
         steps: List[int] = []
         remaining = base_n
         for i in range(len(pts) - 2):
@@ -393,7 +400,57 @@ class AmericanFDMPricer:
             steps.append(ns)
             remaining -= ns
         steps.append(max(1, remaining))
+        return pts, steps
+
+    def _segments(self, n_time: int):
+        divs = self._div_times_tau()
+        pts, steps = self._segments_over([t for t, _ in divs], n_time)
         return divs, pts, steps
+
+    def _job_events(self, n_time: int):
+        """(events, pts, steps, restart) of one grid job on the current grid:
+        events[i] is the ordered list of maps applied to the value vector
+        between segment i and segment i + 1 -- ("div", cash) for a dividend
+        jump, ("ko", ko_lo, ko_hi, rebate) for a knock-out (subclasses) --
+        and restart[i] says whether segment i restarts the Rannacher steps
+        (the reference: the first segment, and every segment of a call,
+        fd_american_equity.py:825-843)."""
+        divs, pts, steps = self._segments(n_time)
+        restart = [seg == 0 or self.option_type == "call" for seg in range(len(steps))]
+        return [[("div", cash)] for _, cash in divs], pts, steps, restart
+
+    def _initial_vector(self) -> np.ndarray:
+        """Value vector at maturity on the current grid."""
+        return self._payoff_array()
+
+    def _make_job(self, key: tuple, sigma: float, n_time: int) -> dict:
+        """The grid job of (sigma, n_time); call with self.sigma = sigma and
+        its grid built."""
+        events, pts, steps, restart = self._job_events(n_time)
+        v = self._initial_vector()
+        # bit for bit the payoff: a device chain then starts from the payoff
+        # slot it uploads instead of sending the vector a second time
+        same = v.tobytes() == self._payoff_array().tobytes()
+        return dict(owner=self, key=key, sigma=sigma, grid=self._grid_state(), events=events,
+                    pts=pts, steps=steps, restart=restart, v=v, v_is_payoff=same)
+
+    def _apply_knockout(self, v, ko_lo: int, ko_hi: int, rebate: float) -> np.ndarray:
+        """Knock-out event on the current grid: nodes j <= ko_lo or j >= ko_hi
+        become max(payoff_j, rebate) -- the holder may exercise an instant
+        before the monitoring time -- and all others keep their value."""
+        v = np.asarray(v, dtype=np.float64)
+        j = np.arange(v.shape[0])
+        knocked = (j <= ko_lo) | (j >= ko_hi)
+        return np.where(knocked, np.maximum(self._payoff_array(), rebate), v)
+
+    def _apply_event(self, v, event: tuple):
+        if event[0] == "div":
+            return self._apply_dividend_jump(v, event[1])
+        return self._apply_knockout(v, event[1], event[2], event[3])
+
+    def _skip_solve(self) -> bool:
+        """True when price and Greeks are known without a solve."""
+        return False
 
     def _state_key(self, sigma: float, n_time: int) -> tuple:
         return (float(sigma), int(n_time), self.spot, self.strike, self.time_to_expiry,
@@ -428,9 +485,7 @@ class AmericanFDMPricer:
             for key, sig, nt in pending:
                 self.sigma = sig
                 self._build_log_grid()
-                divs, pts, steps = self._segments(nt)
-                jobs.append(dict(owner=self, key=key, sigma=sig, grid=self._grid_state(),
-                                 divs=divs, pts=pts, steps=steps, v=self._payoff_array()))
+                jobs.append(self._make_job(key, sig, nt))
         finally:
             self.sigma = sigma0
             self._restore(saved)
@@ -440,8 +495,9 @@ class AmericanFDMPricer:
     def _march_jobs(jobs: list, engine: Engine) -> None:
         """March grid jobs of any number of trades in segment lock-step: every
         job's segment i goes into one engine.run (one launch per distinct
-        (n_nodes, n_time)), then each job's dividend jump, then segment i+1;
-        finally each job's value vector is cached on its owner."""
+        (n_nodes, n_time)), then each job's events at that time (dividend
+        jump, knock-out), then segment i+1; finally each job's value vector
+        is cached on its owner."""
         if not jobs:
             return
         n_seg = max(len(j["steps"]) for j in jobs)
@@ -457,9 +513,8 @@ class AmericanFDMPricer:
                     p._restore(j["grid"])
                     if len(p.s_nodes) - 1 < 2:
                         raise RuntimeError("Spatial grid too coarse.")
-                    restart = seg == 0 or (seg > 0 and p.option_type == "call")
                     solves.append(p._segment_solve(j["v"], j["pts"][seg], j["pts"][seg + 1],
-                                                   j["steps"][seg], restart))
+                                                   j["steps"][seg], j["restart"][seg]))
                 finally:
                     p.sigma = sigma0
                     p._restore(saved)
@@ -468,13 +523,14 @@ class AmericanFDMPricer:
                 for j, v in zip(owners, engine.run(solves)):
                     j["v"] = v
             for j in jobs:
-                if seg < len(j["divs"]):
+                if seg < len(j["events"]):
                     p = j["owner"]
                     sigma0, saved = p.sigma, p._grid_state()
                     try:
                         p.sigma = j["sigma"]
                         p._restore(j["grid"])
-                        j["v"] = p._apply_dividend_jump(j["v"], j["divs"][seg][1])
+                        for event in j["events"][seg]:
+                            j["v"] = p._apply_event(j["v"], event)
                     finally:
                         p.sigma = sigma0
                         p._restore(saved)
@@ -533,9 +589,30 @@ class AmericanFDMPricer:
     def _march_jobs_device(jobs: list, engine: Engine, sess: Session) -> None:
         """_march_jobs with the value vectors in HBM: segment i of every job in
         lock-step launches (initial vectors: the payoff, then the previous
-        segment's slots), the dividend jumps on the device between segments.
-        Leaves each job's final slot in job["slot"]."""
+        segment's slots), the events between segments on the device (the
+        spline jumps into new slots, the knock-outs in place).  A job of more
+        than one segment uploads its payoff once: its marches and knock-outs
+        name that slot.  Leaves each job's final slot in job["slot"]."""
         n_seg = max(len(j["steps"]) for j in jobs)
+        by_n: Dict[int, list] = {}
+        for j in jobs:
+            j["pay"] = None
+            if len(j["steps"]) > 1:
+                by_n.setdefault(len(j["grid"]["s_nodes"]), []).append(j)
+        for js in by_n.values():
+            pay = []
+            for j in js:
+                p = j["owner"]
+                sigma0, saved = p.sigma, p._grid_state()
+                try:
+                    p.sigma = j["sigma"]
+                    p._restore(j["grid"])
+                    pay.append(p._payoff_array())
+                finally:
+                    p.sigma = sigma0
+                    p._restore(saved)
+            for j, sl in zip(js, sess.upload(np.array(pay, dtype=np.float64))):
+                j["pay"] = int(sl)
         for seg in range(n_seg):
             solves, owners = [], []
             for j in jobs:
@@ -548,28 +625,49 @@ class AmericanFDMPricer:
                     p._restore(j["grid"])
                     if len(p.s_nodes) - 1 < 2:
                         raise RuntimeError("Spatial grid too coarse.")
-                    restart = seg == 0 or (seg > 0 and p.option_type == "call")
                     solves.append(p._segment_solve(j["v"], j["pts"][seg], j["pts"][seg + 1],
-                                                   j["steps"][seg], restart))
+                                                   j["steps"][seg], j["restart"][seg]))
                 finally:
                     p.sigma = sigma0
                     p._restore(saved)
                 owners.append(j)
             if solves:
-                vs = None if seg == 0 else [j["slot"] for j in owners]
-                for j, sl in zip(owners, engine.march_slots(sess, solves, vs)):
+                ps = [j["pay"] for j in owners]
+                if seg > 0:
+                    vs = [j["slot"] for j in owners]
+                elif all(j["pay"] is not None and j["v_is_payoff"] for j in owners):
+                    vs = ps  # every chain starts from the payoff it has uploaded
+                else:
+                    vs = None
+                if all(x is None for x in ps):
+                    slots = engine.march_slots(sess, solves, vs)
+                else:
+                    slots = engine.march_slots(sess, solves, vs, ps)
+                for j, sl in zip(owners, slots):
                     j["slot"] = int(sl)
-            jump = [j for j in jobs if seg < len(j["divs"])]
-            by_n: Dict[int, list] = {}
-            for j in jump:
-                by_n.setdefault(len(j["grid"]["s_nodes"]), []).append(j)
-            for js in by_n.values():
-                S = np.array([j["grid"]["s_nodes"] for j in js], dtype=np.float64)
-                cash = [j["divs"][seg][1] for j in js]
-                kc = [(j["owner"]._strike_snapped_for(j) if j["owner"].option_type == "call"
-                       else -1.0) for j in js]
-                for j, sl in zip(js, sess.dividend_jump([j["slot"] for j in js], S, cash, kc)):
-                    j["slot"] = int(sl)
+            # the k-th event of every job at this time, one launch per kind and
+            # grid size (a job's own events keep their order)
+            here = [j for j in jobs if seg < len(j["events"])]
+            for k in range(max((len(j["events"][seg]) for j in here), default=0)):
+                groups: Dict[tuple, list] = {}
+                for j in here:
+                    if k < len(j["events"][seg]):
+                        kind = j["events"][seg][k][0]
+                        groups.setdefault((kind, len(j["grid"]["s_nodes"])), []).append(j)
+                for (kind, n), js in groups.items():
+                    ev = [j["events"][seg][k] for j in js]
+                    if kind == "ko":
+                        sess.knockout([j["slot"] for j in js], n, [e[1] for e in ev],
+                                      [e[2] for e in ev], [e[3] for e in ev],
+                                      [j["pay"] for j in js])
+                        continue
+                    S = np.array([j["grid"]["s_nodes"] for j in js], dtype=np.float64)
+                    cash = [e[1] for e in ev]
+                    kc = [(j["owner"]._strike_snapped_for(j) if j["owner"].option_type == "call"
+                           else -1.0) for j in js]
+                    for j, sl in zip(js, sess.dividend_jump([j["slot"] for j in js], S, cash,
+                                                            kc)):
+                        j["slot"] = int(sl)
 
     def _strike_snapped_for(self, job: dict) -> float:
         st = job["grid"]
@@ -595,10 +693,8 @@ class AmericanFDMPricer:
                 if key not in keys:
                     self.sigma = float(sig)
                     self._build_log_grid()
-                    divs, pts, steps = self._segments(int(nt))
                     keys[key] = len(jobs)
-                    jobs.append(dict(owner=self, key=key, sigma=float(sig), grid=self._grid_state(),
-                                     divs=divs, pts=pts, steps=steps, v=self._payoff_array()))
+                    jobs.append(self._make_job(key, float(sig), int(nt)))
                 index.append(keys[key])
         finally:
             self.sigma = sigma0
@@ -725,20 +821,56 @@ class AmericanFDMPricer:
                 "vega": float(vega), "theta": float(theta)}
 
 
+def _job_slot_bytes(job: dict) -> int:
+    """Bytes of the slots one job's chain creates: one vector per march, one
+    per dividend jump (knock-outs run in place) and the uploaded payoff.  It
+    counts slots, not device memory: the block of every march also holds its
+    copy of the initial vectors, the kernel workspace and, where the payoff
+    slots are not consecutive, the gathered payoff, all kept until the session
+    ends -- several times this figure."""
+    n_jump = sum(1 for evs in job["events"] for e in evs if e[0] == "div")
+    n_seg = len(job["steps"])
+    return 8 * len(job["grid"]["s_nodes"]) * (n_seg + n_jump + (1 if n_seg > 1 else 0))
+
+
 def greeks_many(pricers: Sequence[AmericanFDMPricer], dv_sigma: float = 0.01,
-                price_only: bool = False) -> None:
+                price_only: bool = False, max_slot_bytes: int = 8 << 30) -> None:
     """price_log2 (+ greeks_log2 unless price_only) of many trades in one
     device session: every trade's grids (N, 2N, sigma +-h, +-2h and price_log2's
-    second grid; dividend segments in lock-step with the spline jumps on the
-    device) march in shared launches, and the readouts, Richardson
-    extrapolations, vega and theta run on the device (FDCN_GK_AMERICAN);
-    six numbers per trade come back.  Results land in each pricer's cache."""
+    second grid; the segments between dividends and knock-out dates in
+    lock-step, with the spline jumps and the knock-outs on the device) march
+    in shared launches, and the readouts, Richardson extrapolations, vega and
+    theta run on the device (FDCN_GK_AMERICAN); six numbers per trade come
+    back.  Results land in each pricer's cache.  Vanilla and barrier pricers
+    (american_barrier.py) mix freely.
+
+    Every march creates slots, so the slots of a chain take about n_segments x
+    n_nodes x 8 bytes per grid until its session ends: when that estimate for
+    all trades exceeds max_slot_bytes the trades are processed in consecutive
+    chunks within it (at least one trade each), a fresh session per chunk.
+    max_slot_bytes bounds the slots only; the device memory a session holds is
+    several times larger (_job_slot_bytes)."""
+    pricers = [p for p in pricers if not p._skip_solve()]
     if not pricers:
         return
     engine = pricers[0]._engine()
-    jobs, plan = [], []
+    chunk, chunk_bytes = [], 0
     for p in pricers:
         pj, idx = p._device_jobs(p._device_requests(dv_sigma, price_only))
+        need = sum(_job_slot_bytes(j) for j in pj)
+        if chunk and chunk_bytes + need > max_slot_bytes:
+            _greeks_chunk(chunk, engine, dv_sigma, price_only)
+            chunk, chunk_bytes = [], 0
+        chunk.append((p, pj, idx))
+        chunk_bytes += need
+    _greeks_chunk(chunk, engine, dv_sigma, price_only)
+
+
+def _greeks_chunk(chunk: list, engine: Engine, dv_sigma: float, price_only: bool) -> None:
+    """greeks_many for the trades of one session: (pricer, jobs, job index per
+    request) each."""
+    jobs, plan = [], []
+    for p, pj, idx in chunk:
         plan.append((p, [len(jobs) + i for i in idx]))
         jobs.extend(pj)
     with Session() as S:
@@ -778,7 +910,9 @@ def prefetch_many(pricers: Sequence[AmericanFDMPricer], dv_sigma: float = 0.01,
     dividends are one segment, so the whole set is one engine.run (one launch
     per distinct (n_nodes, n_time)); trades with dividends add one round per
     extra segment, shared by every trade, with the host's spline jumps in
-    between."""
+    between.  Knock-out dates of barrier trades (american_barrier.py) are
+    further segment boundaries, shared in the same way."""
+    pricers = [p for p in pricers if not p._skip_solve()]
     if not pricers:
         return
     if use_richardson and pricers[0]._engine().on_device:

@@ -61,6 +61,17 @@ def tail_quantile() -> float:
 _MON_CACHE: Dict[tuple, frozenset] = {}
 
 
+def rebate_value(rebate_amount: float, rebate_at_hit: bool, carry_rate_nacc: float,
+                 tau: float) -> float:
+    """Value written into knocked-out nodes with `tau` left to maturity
+    (discrete_barrier_fdm_pricer.py:413-440): the amount when it is paid at
+    the hit, else the amount discounted at the carry rate over tau.  Shared
+    with the American knock-out pricer (american_barrier.py)."""
+    if rebate_at_hit:
+        return rebate_amount
+    return rebate_amount * math.exp(-carry_rate_nacc * tau)
+
+
 # 1 + argmin_{1 <= i <= len(s)-2} |s_i - x| for increasing s (first index on
 # ties, as np.argmin), by bisection instead of a full scan
 _nearest_interior = nearest_interior
@@ -435,9 +446,7 @@ class DiscreteBarrierFDMPricer:
                 V[i] = reb
 
     def _rebate(self, tau: float) -> float:
-        if self.rebate_at_hit:
-            return self.rebate_amount
-        return self.rebate_amount * math.exp(-self.carry_rate_nacc * tau)
+        return rebate_value(self.rebate_amount, self.rebate_at_hit, self.carry_rate_nacc, tau)
 
     # ----------------------------------------------------------------- solve
     def _engine(self) -> Engine:

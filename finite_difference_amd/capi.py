@@ -30,7 +30,7 @@ P_HI_C0, P_HI_E0, P_HI_C1, P_HI_E1 = 9, 10, 11, 12
 NPARAM = 13
 I_LO_FORM, I_HI_FORM, I_KO_LO, I_KO_HI, I_MON_START, I_MON_COUNT, I_TAU_MODE = range(7)
 NIPARAM = 7
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 EXPORTED = ("fdcn_cn_batch", "fdcn_it_batch", "fdcn_cn_batch_dev", "fdcn_it_batch_dev",
             "fdcn_plan", "fdcn_sm_extent", "fdcn_log_grid", "fdcn_dividend_jump",
@@ -40,7 +40,8 @@ EXPORTED = ("fdcn_cn_batch", "fdcn_it_batch", "fdcn_cn_batch_dev", "fdcn_it_batc
             "fdcn_abi_version", "fdcn_select_device", "fdcn_current_device",
             "fdcn_tau_sequence", "fdcn_tau_runs", "fdcn_session_create",
             "fdcn_session_destroy", "fdcn_session_slots", "fdcn_session_host_buffer",
-            "fdcn_session_march",
+            "fdcn_session_march", "fdcn_session_march_ps", "fdcn_session_upload",
+            "fdcn_session_knockout",
             "fdcn_session_dividend_jump", "fdcn_session_greeks", "fdcn_session_fetch",
             "fdcn_vc_batch", "fdcn_vc_batch_dev", "fdcn_vc_plan", "fdcn_barrier_plan",
             "fdcn_vmath", "fdcn_american_plan", "fdcn_device_ordinals",

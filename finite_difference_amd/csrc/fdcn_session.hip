@@ -12,7 +12,10 @@
 //
 //   fdcn_session_march          one batched CN/KO or IT launch; initial vectors
 //                               from the host or from earlier slots
+//   fdcn_session_march_ps       the IT march with its payoff in earlier slots
+//   fdcn_session_upload         host vectors into slots (a chain's payoff, once)
 //   fdcn_session_dividend_jump  spline remap of slots into new slots (device)
+//   fdcn_session_knockout       monitoring-date knock-out of slots, in place
 //   fdcn_session_greeks         per-trade readouts + combinations -> T x 6
 //                               scalars back to the host
 //   fdcn_session_fetch          whole vectors back (when a caller wants them)
@@ -102,6 +105,27 @@ __global__ void gather_rows(const uint64_t* __restrict__ src, double* __restrict
   const double* s = reinterpret_cast<const double*>(src[blockIdx.x]);
   double* d = dst + (size_t)blockIdx.x * n;
   for (int i = threadIdx.x; i < n; i += blockDim.x) d[i] = s[i];
+}
+
+// Knock-out event between two segments of an American march: on the knocked
+// nodes (j <= ko_lo or j >= ko_hi) of vector b, V_j <- max(floor_j, R_b), or
+// V_j <- R_b without a floor; every other node is left alone.  Threads run
+// along the nodes (`chunks` workgroups of 256 per vector, one launch for the
+// batch), so the floor loads and the stores are contiguous 8-byte accesses.
+// max keeps the floor on ties and passes its NaN on, as np.maximum(floor, R).
+__global__ void __launch_bounds__(256)
+knockout_kernel(int n, int chunks, const uint64_t* __restrict__ dst,
+                const uint64_t* __restrict__ floor_src, const int32_t* __restrict__ ko_lo,
+                const int32_t* __restrict__ ko_hi, const double* __restrict__ rebate) {
+  const int b = blockIdx.x / chunks;
+  const int j = (blockIdx.x % chunks) * 256 + threadIdx.x;
+  if (j >= n || (j > ko_lo[b] && j < ko_hi[b])) return;
+  double x = rebate[b];
+  if (floor_src) {
+    const double f = reinterpret_cast<const double*>(floor_src[b])[j];
+    x = (f >= x || f != f) ? f : x;
+  }
+  reinterpret_cast<double*>(dst[b])[j] = x;
 }
 
 // Dividend jump of one value vector per workgroup (fd_american_equity.py
@@ -509,11 +533,13 @@ int fdcn_session_host_buffer(fdcn_session* s, int64_t bytes, void** out) {
   return FDCN_OK;
 }
 
-int fdcn_session_march(fdcn_session* s, int32_t it, int32_t B, int32_t n_nodes, int32_t n_time,
-                       int32_t n_ranna, const double* params, const int32_t* iparams,
-                       const double* v_init, const int32_t* v_init_slots, const double* payoff,
-                       int32_t n_mon, const int32_t* mon_step, const double* mon_rebate,
-                       int32_t* out_slots) {
+// fdcn_session_march and fdcn_session_march_ps: the IT payoff is the host
+// array `payoff` or the vectors in `payoff_slots` (at most one of them)
+static int session_march(fdcn_session* s, int32_t it, int32_t B, int32_t n_nodes, int32_t n_time,
+                         int32_t n_ranna, const double* params, const int32_t* iparams,
+                         const double* v_init, const int32_t* v_init_slots,
+                         const double* payoff, const int32_t* payoff_slots, int32_t n_mon,
+                         const int32_t* mon_step, const double* mon_rebate, int32_t* out_slots) {
   if (!s) return sfail(FDCN_EINVAL, "NULL session");
   it = it ? 1 : 0;
   int rc = fdcn_internal::validate_plan(it, B, n_nodes, n_time, n_ranna, params, iparams, n_mon,
@@ -523,8 +549,16 @@ int fdcn_session_march(fdcn_session* s, int32_t it, int32_t B, int32_t n_nodes, 
   if (!out_slots) return sfail(FDCN_EINVAL, "NULL out_slots");
   if ((v_init == nullptr) == (v_init_slots == nullptr))
     return sfail(FDCN_EINVAL, "pass exactly one of v_init (host) and v_init_slots");
-  if (it && !payoff) return sfail(FDCN_EINVAL, "IT march without payoff");
+  if (it && !payoff && !payoff_slots) return sfail(FDCN_EINVAL, "IT march without payoff");
   if (v_init_slots && (rc = check_slots(s, B, v_init_slots, n_nodes))) return rc;
+  if (payoff_slots && (rc = check_slots(s, B, payoff_slots, n_nodes))) return rc;
+  // payoff slots that are consecutive vectors of one block (one upload) are
+  // the [B][n_nodes] array the march reads; any other set is gathered into one
+  bool ps_gather = false;
+  for (int32_t b = 1; payoff_slots && b < B; ++b)
+    if ((uint64_t)s->slots.ptr[payoff_slots[b]] !=
+        (uint64_t)s->slots.ptr[payoff_slots[0]] + sizeof(double) * (uint64_t)b * n_nodes)
+      ps_gather = true;
   const int k_cap = fdcn_sm_extent(B, n_nodes, n_time, n_ranna, params);
   if (k_cap < 0) return k_cap;
   int32_t w_, npt_, spb_, lds_;
@@ -540,8 +574,9 @@ int fdcn_session_march(fdcn_session* s, int32_t it, int32_t B, int32_t n_nodes, 
   const size_t oM = L.add(sizeof(int32_t) * nm);
   const size_t oR = L.add(sizeof(double) * nm);
   const size_t oA = v_init_slots ? L.add(sizeof(uint64_t) * B) : 0;
+  const size_t oAF = ps_gather ? L.add(sizeof(uint64_t) * B) : 0;
   const size_t pre = L.size;  // the small inputs: [0, pre)
-  const size_t oF = it ? L.add(vb) : 0;
+  const size_t oF = it && (!payoff_slots || ps_gather) ? L.add(vb) : 0;
   // an IT march whose host v_init is its payoff array (the first segment of
   // an American grid) copies that array once and reads it twice
   const bool v_is_payoff = it && v_init && v_init == payoff;
@@ -554,10 +589,11 @@ int fdcn_session_march(fdcn_session* s, int32_t it, int32_t B, int32_t n_nodes, 
   // the device from where it lies; anything else is staged.  The staging
   // block mirrors the device offsets up to the first array copied directly,
   // so the common all-staged case is one H2D copy.
-  const bool f_direct = it && s->pinned().owns(payoff, vb);
+  const bool f_host = it && !payoff_slots;
+  const bool f_direct = f_host && s->pinned().owns(payoff, vb);
   const bool v_host = v_init && !v_is_payoff;
   const bool v_direct = v_host && s->pinned().owns(v_init, vb);
-  const bool stage_f = it && !f_direct, stage_v = v_host && !v_direct;
+  const bool stage_f = f_host && !f_direct, stage_v = v_host && !v_direct;
   size_t hsz = pre, hF = 0, hV = 0;
   if (stage_f) hF = hsz, hsz = oF + al256(vb);
   if (stage_v) hV = it ? (stage_f ? oV : pre) : oV, hsz = hV + al256(vb);
@@ -575,11 +611,16 @@ int fdcn_session_march(fdcn_session* s, int32_t it, int32_t B, int32_t n_nodes, 
     uint64_t* a = (uint64_t*)(h + oA);
     for (int32_t b = 0; b < B; ++b) a[b] = (uint64_t)s->slots.ptr[v_init_slots[b]];
   }
+  if (ps_gather) {
+    uint64_t* a = (uint64_t*)(h + oAF);
+    for (int32_t b = 0; b < B; ++b) a[b] = (uint64_t)s->slots.ptr[payoff_slots[b]];
+  }
   if (stage_f) stage_copy(h + hF, payoff, vb);
   if (stage_v) stage_copy(h + hV, v_init, vb);
   hipStream_t st;
   if ((rc = pick_stream(s, &st))) return rc;
   if (v_init_slots && (rc = wait_producers(s, st, B, v_init_slots))) return rc;
+  if (payoff_slots && (rc = wait_producers(s, st, B, payoff_slots))) return rc;
   char* d = nullptr;
   if ((rc = alloc_block(s, st, L.size, &d))) return rc;
   S_TRY(hipMemcpyAsync(d, h, mirrored, hipMemcpyHostToDevice, st));
@@ -591,10 +632,17 @@ int fdcn_session_march(fdcn_session* s, int32_t it, int32_t B, int32_t n_nodes, 
                        (double*)(d + oV), n_nodes);
     S_TRY(hipGetLastError());
   }
+  if (ps_gather) {
+    hipLaunchKernelGGL(gather_rows, dim3(B), dim3(256), 0, st, (const uint64_t*)(d + oAF),
+                       (double*)(d + oF), n_nodes);
+    S_TRY(hipGetLastError());
+  }
+  const double* d_payoff = payoff_slots && !ps_gather ? s->slots.ptr[payoff_slots[0]]
+                                                      : (const double*)(d + oF);
   rc = fdcn_internal::launch_march(it, B, n_nodes, n_time, n_ranna, (const double*)(d + oP),
                                    (const int32_t*)(d + oI),
                                    (const double*)(d + (v_is_payoff ? oF : oV)),
-                                   it ? (const double*)(d + oF) : nullptr, n_mon,
+                                   it ? d_payoff : nullptr, n_mon,
                                    (const int32_t*)(d + oM), (const double*)(d + oR),
                                    (double*)(d + oO), k_cap, (double*)(d + oW),
                                    (int64_t)ws_bytes, st);
@@ -602,6 +650,121 @@ int fdcn_session_march(fdcn_session* s, int32_t it, int32_t B, int32_t n_nodes, 
   int32_t ev;
   if ((rc = record(s, st, &ev))) return rc;
   return new_slots(s, (double*)(d + oO), B, n_nodes, ev, out_slots);
+}
+
+int fdcn_session_march(fdcn_session* s, int32_t it, int32_t B, int32_t n_nodes, int32_t n_time,
+                       int32_t n_ranna, const double* params, const int32_t* iparams,
+                       const double* v_init, const int32_t* v_init_slots, const double* payoff,
+                       int32_t n_mon, const int32_t* mon_step, const double* mon_rebate,
+                       int32_t* out_slots) {
+  return session_march(s, it, B, n_nodes, n_time, n_ranna, params, iparams, v_init, v_init_slots,
+                       payoff, nullptr, n_mon, mon_step, mon_rebate, out_slots);
+}
+
+int fdcn_session_march_ps(fdcn_session* s, int32_t it, int32_t B, int32_t n_nodes,
+                          int32_t n_time, int32_t n_ranna, const double* params,
+                          const int32_t* iparams, const double* v_init,
+                          const int32_t* v_init_slots, const int32_t* payoff_slots,
+                          int32_t n_mon, const int32_t* mon_step, const double* mon_rebate,
+                          int32_t* out_slots) {
+  if (B < 1 || n_nodes < 1) return sfail(FDCN_EINVAL, "march_ps: B >= 1, n_nodes >= 1");
+  if (!it) return sfail(FDCN_EINVAL, "march_ps: payoff slots belong to an IT march (it != 0)");
+  if (!payoff_slots) return sfail(FDCN_EINVAL, "march_ps: NULL payoff_slots");
+  return session_march(s, it, B, n_nodes, n_time, n_ranna, params, iparams, v_init, v_init_slots,
+                       nullptr, payoff_slots, n_mon, mon_step, mon_rebate, out_slots);
+}
+
+int fdcn_session_upload(fdcn_session* s, int32_t B, int32_t n_nodes, const double* v,
+                        int32_t* out_slots) {
+  if (B < 1 || n_nodes < 1) return sfail(FDCN_EINVAL, "upload: B >= 1, n_nodes >= 1");
+  if (!v || !out_slots) return sfail(FDCN_EINVAL, "upload: NULL argument");
+  if (!s) return sfail(FDCN_EINVAL, "NULL session");
+  const size_t vb = sizeof(double) * (size_t)B * n_nodes;
+  const void* src = v;  // inside the session's pinned memory: read where it lies
+  if (!s->pinned().owns(v, vb)) {
+    char* h = s->pinned().get(vb);
+    if (!h) return sfail(FDCN_ENOMEM, "hipHostMalloc(%zu) failed", vb);
+    stage_copy(h, v, vb);
+    src = h;
+  }
+  hipStream_t st;
+  int rc = pick_stream(s, &st);
+  if (rc) return rc;
+  char* d = nullptr;
+  if ((rc = alloc_block(s, st, vb, &d))) return rc;
+  S_TRY(hipMemcpyAsync(d, src, vb, hipMemcpyHostToDevice, st));
+  int32_t ev;
+  if ((rc = record(s, st, &ev))) return rc;
+  return new_slots(s, (double*)d, B, n_nodes, ev, out_slots);
+}
+
+int fdcn_session_knockout(fdcn_session* s, int32_t B, int32_t n_nodes, const int32_t* slots,
+                          const int32_t* ko_lo, const int32_t* ko_hi, const double* rebate,
+                          const int32_t* floor_slots) {
+  if (B < 1 || n_nodes < 1) return sfail(FDCN_EINVAL, "knockout: B >= 1, n_nodes >= 1");
+  if (!slots || !ko_lo || !ko_hi || !rebate)
+    return sfail(FDCN_EINVAL, "knockout: NULL argument (slots, ko_lo, ko_hi, rebate)");
+  if (!s) return sfail(FDCN_EINVAL, "NULL session");
+  const int64_t chunks = ((int64_t)n_nodes + 255) / 256;
+  if (chunks * B > INT32_MAX) return sfail(FDCN_EINVAL, "knockout: batch too large for one launch");
+  int rc = check_slots(s, B, slots, n_nodes);
+  if (rc) return rc;
+  if (floor_slots && (rc = check_slots(s, B, floor_slots, n_nodes))) return rc;
+  // the event writes in place: a slot named twice, or read as a floor while
+  // another vector's event writes it, would make the result depend on timing
+  std::vector<int32_t> sorted(slots, slots + B);
+  std::sort(sorted.begin(), sorted.end());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+    return sfail(FDCN_EINVAL, "knockout: a slot appears twice in slots");
+  for (int32_t b = 0; floor_slots && b < B; ++b)
+    if (std::binary_search(sorted.begin(), sorted.end(), floor_slots[b]))
+      return sfail(FDCN_EINVAL, "knockout: floor slot %d is one of slots", floor_slots[b]);
+  Layout L;
+  const size_t oA = L.add(sizeof(uint64_t) * B);
+  const size_t oF = L.add(sizeof(uint64_t) * B);
+  const size_t oLo = L.add(sizeof(int32_t) * B);
+  const size_t oHi = L.add(sizeof(int32_t) * B);
+  const size_t oR = L.add(sizeof(double) * B);
+  char* h = s->pinned().get(L.size);
+  if (!h) return sfail(FDCN_ENOMEM, "hipHostMalloc(%zu) failed", L.size);
+  uint64_t* a = (uint64_t*)(h + oA);
+  uint64_t* f = (uint64_t*)(h + oF);
+  for (int32_t b = 0; b < B; ++b) {
+    a[b] = (uint64_t)s->slots.ptr[slots[b]];
+    f[b] = floor_slots ? (uint64_t)s->slots.ptr[floor_slots[b]] : 0;
+  }
+  memcpy(h + oLo, ko_lo, sizeof(int32_t) * B);
+  memcpy(h + oHi, ko_hi, sizeof(int32_t) * B);
+  memcpy(h + oR, rebate, sizeof(double) * B);
+  hipStream_t st;
+  if ((rc = pick_stream(s, &st))) return rc;
+  // In place: the event runs after everything the session has queued so far,
+  // on every stream -- the march that produced the slots (and the upload of
+  // the floor), and any earlier call that still reads them.  Deliberately
+  // conservative: one fresh event per other stream (up to 3 a call, kept
+  // until destroy) instead of the slots' producer events plus a per-slot
+  // "last reader", which the slot table does not keep.  It joins the
+  // session's streams at every monitoring date, so launch groups of
+  // different shapes overlap within a segment round but not across one.
+  for (hipStream_t other : s->streams) {
+    if (other == st) continue;
+    int32_t ev;
+    if ((rc = record(s, other, &ev))) return rc;
+    S_TRY(hipStreamWaitEvent(st, s->events[ev], 0));
+  }
+  char* d = nullptr;
+  if ((rc = alloc_block(s, st, L.size, &d))) return rc;
+  S_TRY(hipMemcpyAsync(d, h, L.size, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(knockout_kernel, dim3((unsigned)(chunks * B)), dim3(256), 0, st, n_nodes,
+                     (int)chunks, (const uint64_t*)(d + oA),
+                     floor_slots ? (const uint64_t*)(d + oF) : nullptr,
+                     (const int32_t*)(d + oLo), (const int32_t*)(d + oHi),
+                     (const double*)(d + oR));
+  S_TRY(hipGetLastError());
+  int32_t ev;
+  if ((rc = record(s, st, &ev))) return rc;
+  for (int32_t b = 0; b < B; ++b) s->slots.ev[(size_t)slots[b]] = ev;  // consumers wait for it
+  return FDCN_OK;
 }
 
 int fdcn_session_dividend_jump(fdcn_session* s, int32_t B, int32_t n_nodes,

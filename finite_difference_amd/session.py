@@ -48,6 +48,13 @@ def _bind(L: ctypes.CDLL) -> None:
     L.fdcn_session_host_buffer.argtypes = [_V, ctypes.c_int64, ctypes.POINTER(_V)]
     L.fdcn_session_march.restype = _I
     L.fdcn_session_march.argtypes = [_V, _I, _I, _I, _I, _I, _V, _V, _V, _V, _V, _I, _V, _V, _V]
+    L.fdcn_session_march_ps.restype = _I
+    L.fdcn_session_march_ps.argtypes = [_V, _I, _I, _I, _I, _I, _V, _V, _V, _V, _V, _I, _V, _V,
+                                        _V]
+    L.fdcn_session_upload.restype = _I
+    L.fdcn_session_upload.argtypes = [_V, _I, _I, _V, _V]
+    L.fdcn_session_knockout.restype = _I
+    L.fdcn_session_knockout.argtypes = [_V, _I, _I, _V, _V, _V, _V, _V]
     L.fdcn_session_dividend_jump.restype = _I
     L.fdcn_session_dividend_jump.argtypes = [_V, _I, _I, _V, _V, _V, _V, _V]
     L.fdcn_session_greeks.restype = _I
@@ -215,21 +222,63 @@ class Session:
         return np.asarray(owner)[:int(n)]
 
     # -- steps ---------------------------------------------------------------
-    def march(self, g, v_init_slots: Optional[np.ndarray] = None) -> np.ndarray:
+    def march(self, g, v_init_slots: Optional[np.ndarray] = None,
+              payoff_slots: Optional[np.ndarray] = None) -> np.ndarray:
         """One batched launch of an engine.Group; returns its B output slots.
-        With v_init_slots the initial vectors are those slots (g.v_init unused)."""
+        With v_init_slots the initial vectors are those slots (g.v_init unused).
+        With payoff_slots (IT groups) the exercise values are those slots
+        (fdcn_session_march_ps; g.payoff is not sent)."""
         out = np.empty(g.B, dtype=np.int32)
         vs = None if v_init_slots is None else np.ascontiguousarray(v_init_slots, np.int32)
         vi = None if vs is not None else np.ascontiguousarray(g.v_init, np.float64)
         P = np.ascontiguousarray(g.params, np.float64)
         I = np.ascontiguousarray(g.iparams, np.int32)
-        F = np.ascontiguousarray(g.payoff, np.float64) if g.it else None
         ms = np.ascontiguousarray(g.mon_step if len(g.mon_step) else [0], np.int32)
         mr = np.ascontiguousarray(g.mon_rebate if len(g.mon_rebate) else [0.0], np.float64)
+        if payoff_slots is not None:
+            if not g.it:
+                raise ValueError("payoff_slots belong to an IT group")
+            ps = np.ascontiguousarray(payoff_slots, np.int32)
+            if ps.shape != (g.B,) or (vs is not None and vs.shape != (g.B,)):
+                raise ValueError("march: one slot per scenario")
+            capi._check(self._L.fdcn_session_march_ps(
+                self._h, 1, g.B, g.n_nodes, g.n_time, g.n_ranna, _ptr(P), _ptr(I), _ptr(vi),
+                _ptr(vs), _ptr(ps), len(g.mon_step), _ptr(ms), _ptr(mr), _ptr(out)))
+            return out
+        F = np.ascontiguousarray(g.payoff, np.float64) if g.it else None
         capi._check(self._L.fdcn_session_march(
             self._h, 1 if g.it else 0, g.B, g.n_nodes, g.n_time, g.n_ranna, _ptr(P), _ptr(I),
             _ptr(vi), _ptr(vs), _ptr(F), len(g.mon_step), _ptr(ms), _ptr(mr), _ptr(out)))
         return out
+
+    def upload(self, v) -> np.ndarray:
+        """Host vectors v [B, n_nodes] into B new slots (fdcn_session_upload).
+        An array from host_buffer is read in place, asynchronously (leave it
+        unchanged until the next greeks / fetch); any other is staged."""
+        V = np.ascontiguousarray(v, np.float64)
+        if V.ndim != 2:
+            raise ValueError("upload: v must be [B, n_nodes]")
+        B, n = V.shape
+        out = np.empty(B, dtype=np.int32)
+        capi._check(self._L.fdcn_session_upload(self._h, B, n, _ptr(V), _ptr(out)))
+        return out
+
+    def knockout(self, slots, n_nodes: int, ko_lo, ko_hi, rebate,
+                 floor_slots=None) -> None:
+        """Knock-out event in place on `slots` (fdcn_session_knockout): nodes
+        j <= ko_lo[b] or j >= ko_hi[b] of vector b become max(floor_j, rebate[b])
+        with the floor vectors in floor_slots, or rebate[b] without them."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        B = sl.shape[0]
+        lo = np.ascontiguousarray(ko_lo, np.int32)
+        hi = np.ascontiguousarray(ko_hi, np.int32)
+        R = np.ascontiguousarray(rebate, np.float64)
+        fs = None if floor_slots is None else np.ascontiguousarray(floor_slots, np.int32)
+        if (sl.ndim != 1 or lo.shape != (B,) or hi.shape != (B,) or R.shape != (B,)
+                or (fs is not None and fs.shape != (B,))):
+            raise ValueError("knockout: one threshold pair, rebate and floor slot per slot")
+        capi._check(self._L.fdcn_session_knockout(self._h, B, int(n_nodes), _ptr(sl), _ptr(lo),
+                                                  _ptr(hi), _ptr(R), _ptr(fs)))
 
     def dividend_jump(self, slots, s_nodes: np.ndarray, cash, strike_call) -> np.ndarray:
         sl = np.ascontiguousarray(slots, np.int32)

@@ -45,7 +45,10 @@
 extern "C" {
 #endif
 
-/* 7: the BGK barrier pricer's Monte Carlo entry points (fdcn_mc_bgk_batch,
+/* 8: fdcn_session_upload, fdcn_session_knockout and fdcn_session_march_ps (the
+ * American knock-out chain: monitoring events between IT segments) were added
+ * after 7.
+ * 7: the BGK barrier pricer's Monte Carlo entry points (fdcn_mc_bgk_batch,
  * fdcn_mc_bgk_batch_dev, fdcn_mc_bgk_plan) were added after 6.
  * 6: the Monte Carlo discrete-barrier entry points (fdcn_mc_barrier_batch,
  * fdcn_mc_barrier_batch_dev, fdcn_mc_plan; fdcn_mc_normals in fdcn_diag.h)
@@ -54,7 +57,7 @@ extern "C" {
  * spot-space kernels (fdcn_vc_force_variant / _variant_name / _forms) and the
  * fdcn_vc workspace contract (+16 doubles per scenario) changed the exported
  * surface after 4 */
-#define FDCN_ABI_VERSION 7
+#define FDCN_ABI_VERSION 8
 
 /* ---- per-scenario fp64 parameters: params[b*FDCN_NPARAM + k] ---------- */
 enum fdcn_param {
@@ -214,6 +217,46 @@ int fdcn_session_dividend_jump(fdcn_session* s, int32_t B, int32_t n_nodes,
                                const int32_t* in_slots, const double* s_nodes,
                                const double* cash_div, const double* strike_call,
                                int32_t* out_slots);
+
+/* Host vectors v [B][n_nodes] become B new slots (numbers into out_slots
+ * [B]): the payoff of an American chain, uploaded once and then named by
+ * fdcn_session_march_ps / fdcn_session_knockout.  Staged through pinned memory
+ * before the call returns, or, for an array inside an
+ * fdcn_session_host_buffer region, read in place by the asynchronous copy (as
+ * fdcn_session_march does).  B >= 1, n_nodes >= 1. */
+int fdcn_session_upload(fdcn_session* s, int32_t B, int32_t n_nodes, const double* v,
+                        int32_t* out_slots);
+
+/* Knock-out event of a discretely monitored American option, in place on
+ * `slots` [B] (no new slot):
+ *   V_j <- max(floor_j, rebate[b])   for j <= ko_lo[b] or j >= ko_hi[b]
+ * with floor the vector in floor_slots[b] (the exercise value: the holder may
+ * exercise an instant before the monitoring time); all other nodes keep their
+ * value.  floor_slots == NULL: V_j <- rebate[b] (the plain projection).
+ * Thresholds follow FDCN_I_KO_LO / FDCN_I_KO_HI (-1 / >= n_nodes: none on
+ * that side); ko_lo[b] >= ko_hi[b] is allowed and knocks every node.
+ * Bit-identical to np.where(knocked, np.maximum(floor, R), V).  The event is
+ * ordered after every call the session queued before it (the march that
+ * produced the slots, and any earlier reader of them); later consumers of the
+ * slots wait for it.  B >= 1, n_nodes >= 1; a slot may appear once in
+ * `slots`, and no floor slot may be one of `slots`. */
+int fdcn_session_knockout(fdcn_session* s, int32_t B, int32_t n_nodes, const int32_t* slots,
+                          const int32_t* ko_lo, const int32_t* ko_hi, const double* rebate,
+                          const int32_t* floor_slots);
+
+/* fdcn_session_march for an Ikonen-Toivanen march (it != 0 required) whose
+ * payoff lies in earlier slots (payoff_slots [B], e.g. from
+ * fdcn_session_upload) instead of a host array: a chain of segments names the
+ * payoff it uploaded once rather than sending it with every march.  Slots
+ * that are consecutive vectors of one block are read where they lie,
+ * otherwise they are gathered on the device.  Same arithmetic, bit for bit,
+ * as fdcn_session_march with the same payoff values.  B >= 1. */
+int fdcn_session_march_ps(fdcn_session* s, int32_t it, int32_t B, int32_t n_nodes,
+                          int32_t n_time, int32_t n_ranna, const double* params,
+                          const int32_t* iparams, const double* v_init,
+                          const int32_t* v_init_slots, const int32_t* payoff_slots,
+                          int32_t n_mon, const int32_t* mon_step, const double* mon_rebate,
+                          int32_t* out_slots);
 
 /* Greeks epilogue: T trades, trade t of kind[t] reads readouts first[t] ..
  * first[t]+k-1 (k per kind below) and writes out[t][FDCN_GK_NOUT] =

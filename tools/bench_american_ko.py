@@ -1,0 +1,248 @@
+#!/usr/bin/env python3
+"""Time of one American knock-out chain on the device session
+(csrc/fdcn_session.hip: fdcn_session_march_ps + fdcn_session_knockout).
+
+Workload: the American throughput configuration's trade and grid (the
+notebook put over a strike x vol sweep, 2048 x 4096, 4096 scenarios) as a
+down-and-out put monitored on every weekday: 23 segments, 22 knock-out events.
+Every scenario shares the dates, so each segment is one launch for the batch.
+
+Three times, same process, same grid and batch:
+
+  chain       upload the payoff once, then per segment fdcn_session_march_ps
+              and fdcn_session_knockout; ends with the price readout (which
+              waits for the chain).  Wall clock around the calls.
+  chain_host  the same chain through fdcn_session_march, which sends the
+              payoff from the host with every segment.
+  plain       one fdcn_it_batch_dev launch of all the steps (the vanilla
+              American march: the code every segment runs), device events.
+
+The chains are timed on the host clock and the plain launch with device
+events, so chain_over_plain compares two clocks (a chain's kernel time needs
+a kernel trace of this tool).  The launch plans are built before the clock
+starts (the facade's own
+_job_events / _segment_solve per scenario); the first scenarios are checked
+against the facade's session path.  Prints one JSON line.  --dump-outputs DIR
+writes the chain's prices as DIR/american_ko_prices.npy.  Without a GPU it
+fails; there is no fallback.
+"""
+from __future__ import annotations
+
+import argparse
+import datetime as dt
+import json
+import math
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+VAL, MAT = dt.date(2025, 7, 28), dt.date(2025, 8, 28)
+SPOT = 176.39
+
+
+def weekdays():
+    days = [VAL + dt.timedelta(days=k) for k in range((MAT - VAL).days + 1)]
+    return [d for d in days if d.weekday() < 5]
+
+
+def build_jobs(B: int, n_space: int, n_time: int, barrier: float, seed: int = 0):
+    """One grid job per scenario: a single pricer re-pointed at each trade of
+    the sweep (same dates and curve), as bench.py builds the vanilla batch."""
+    from finite_difference_amd import AmericanBarrierFDMPricer, market
+    curve = market.iso_curve(market.create_rate_df(math.exp(0.07053828272) - 1.0))
+    p, jobs = None, []
+    for i in range(B):
+        j = (i * 2654435761 + seed * 97) % B
+        strike = 140.0 + 70.0 * (j % 64) / 63.0
+        sigma = 0.18 + 0.30 * ((j // 64) % 64) / 63.0
+        if p is None:
+            p = AmericanBarrierFDMPricer(
+                spot=SPOT, strike=strike, valuation_date=VAL, maturity_date=MAT, sigma=sigma,
+                option_type="put", discount_curve=curve, forward_curve=curve,
+                num_space_nodes=n_space, num_time_steps=n_time, rannacher_steps=2,
+                barrier_type="down-and-out", lower_barrier=barrier, monitor_dates=weekdays())
+        p._reset_trade(SPOT, strike, sigma)
+        p._build_log_grid()
+        jobs.append(p._make_job(p._state_key(sigma, n_time), sigma, n_time))
+    return p, jobs
+
+
+def segment_groups(p, jobs, n_time: int):
+    """The launch group of every segment (all scenarios share pts / steps),
+    and the group of the unsegmented march."""
+    from finite_difference_amd import capi
+    from finite_difference_amd.engine import Group, pack
+    j0 = jobs[0]
+    assert all(j["pts"] == j0["pts"] and j["steps"] == j0["steps"] for j in jobs)
+    solves = []
+    for j in jobs:
+        p.sigma = j["sigma"]
+        p._restore(j["grid"])
+        solves.append(p._segment_solve(j["v"], j0["pts"][0], j0["pts"][1], j0["steps"][0],
+                                       j0["restart"][0]))
+    g0 = pack(solves, list(range(len(solves))))
+    del solves
+
+    def variant(tau0, tau1, steps, restart):
+        P = g0.params.copy()
+        P[:, capi.P_DT] = (tau1 - tau0) / float(steps)
+        P[:, capi.P_TAU0] = tau0
+        return Group(True, g0.n_nodes, int(steps), p.rannacher_steps if restart else 0, P,
+                     g0.iparams, g0.v_init, g0.payoff, g0.mon_step, g0.mon_rebate, g0.index)
+    groups = [variant(j0["pts"][s], j0["pts"][s + 1], j0["steps"][s], j0["restart"][s])
+              for s in range(len(j0["steps"]))]
+    assert np.array_equal(groups[0].params, g0.params)
+    plain = variant(0.0, p.time_to_expiry, n_time, True)
+    plain.v_init = g0.payoff  # the vanilla march starts from the payoff
+    return groups, plain
+
+
+def run_chain(p, jobs, groups, payoff_slots: bool):
+    """One chain in a fresh session: (seconds from the first call to the end
+    of the readout's wait, (seconds of the host calls that queue the chain,
+    seconds of the payoff upload call among them), prices)."""
+    from finite_difference_amd.session import GK_READOUT, Session
+    n = groups[0].n_nodes
+    ev = [[j["events"][s][0] for j in jobs] for s in range(len(groups) - 1)]
+    lo = [np.array([e[1] for e in es], np.int32) for es in ev]
+    hi = [np.array([e[2] for e in es], np.int32) for es in ev]
+    reb = [np.array([e[3] for e in es]) for es in ev]
+    # with rebate 0 the knock-out of the payoff at maturity leaves it as it is:
+    # the chain then starts from the payoff slot (the facade does the same)
+    from_slot = payoff_slots and all(j["v_is_payoff"] for j in jobs)
+    with Session() as S:
+        t0 = time.perf_counter()
+        pay = S.upload(groups[0].payoff)
+        t_upload = time.perf_counter() - t0
+        slots = pay if from_slot else None
+        for s, g in enumerate(groups):
+            slots = S.march(g, slots, pay) if payoff_slots else S.march(g, slots)
+            if s < len(ev):
+                S.knockout(slots, n, lo[s], hi[s], reb[s], pay)
+        t_queued = time.perf_counter() - t0
+        trades = [(GK_READOUT, [p._job_readout(j, int(sl), False)], ())
+                  for j, sl in zip(jobs, slots)]
+        t1 = time.perf_counter()
+        out = S.greeks(trades)  # waits for the chain
+        t_wait = time.perf_counter() - t1
+    # the readout plan is host work of this tool, not of the chain: the chain's
+    # time is its calls plus the wait for the device
+    return t_queued + t_wait, (t_queued, t_upload), out[:, 0].copy()
+
+
+def run_plain(g, launches: int, warmup: int):
+    import torch
+    from finite_difference_amd import capi
+    dev = torch.device("cuda:0")
+    k_cap = capi.sm_extent(g.n_nodes, g.n_time, g.n_ranna, g.params)
+    plan = capi.plan(g.n_nodes, True, k_cap, n_time=g.n_time, B=g.B)
+    P, I = torch.from_numpy(g.params).to(dev), torch.from_numpy(g.iparams).to(dev)
+    V0, F = torch.from_numpy(g.v_init).to(dev), torch.from_numpy(g.payoff).to(dev)
+    out = torch.empty_like(V0)
+    ws_bytes = max(8, plan["ws_bytes_per_scen"] * g.B)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream()
+
+    def launch():
+        capi.it_batch_dev(g.B, g.n_nodes, g.n_time, g.n_ranna, P.data_ptr(), I.data_ptr(),
+                          V0.data_ptr(), F.data_ptr(), out.data_ptr(), k_cap, ws.data_ptr(),
+                          ws_bytes, stream.cuda_stream)
+    for _ in range(warmup):
+        launch()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(launches):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        launch()
+        e1.record(stream)
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1) * 1e-3)
+    return times, torch.cuda.get_device_name(0)
+
+
+def facade_parity(p, jobs, prices, count: int = 3):
+    """The first scenarios through the facade's own session path."""
+    from finite_difference_amd.american import AmericanFDMPricer
+    from finite_difference_amd.session import GK_READOUT, Session
+    sub = [dict(j) for j in jobs[:count]]
+    with Session() as S:
+        AmericanFDMPricer._march_jobs_device(sub, p._engine(), S)
+        out = S.greeks([(GK_READOUT, [p._job_readout(j, j["slot"], False)], ()) for j in sub])
+    worst = max(abs(float(a) - float(b)) / max(1.0, abs(float(b)))
+                for a, b in zip(prices[:count], out[:, 0]))
+    return {"scenarios": count, "worst_rel_price_diff": worst, "bound": 1e-9,
+            "ok": bool(worst <= 1e-9)}
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--n-space", type=int, default=2048)
+    ap.add_argument("--n-time", type=int, default=4096)
+    ap.add_argument("--barrier", type=float, default=150.0, help="down-and-out level")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR")
+    args = ap.parse_args()
+
+    from finite_difference_amd import capi
+    capi.require_device()
+    t0 = time.perf_counter()
+    p, jobs = build_jobs(args.batch, args.n_space, args.n_time, args.barrier)
+    groups, plain = segment_groups(p, jobs, args.n_time)
+    t_plan = time.perf_counter() - t0
+
+    res = {}
+    for name, ps in (("chain", True), ("chain_host", False)):
+        runs = [run_chain(p, jobs, groups, ps) for _ in range(args.warmup + args.reps)]
+        runs = runs[args.warmup:]
+        res[name] = {"seconds": [r[0] for r in runs], "queued": [r[1][0] for r in runs],
+                     "upload": [r[1][1] for r in runs], "prices": runs[-1][2]}
+    plain_t, device = run_plain(plain, args.reps, args.warmup)
+    chain = statistics.median(res["chain"]["seconds"])
+    chain_host = statistics.median(res["chain_host"]["seconds"])
+    plain_med = statistics.median(plain_t)
+    prices = res["chain"]["prices"]
+    line = {
+        "metric": "american_ko_chain_ms",
+        "value": chain * 1e3,
+        "device": device,
+        "batch": args.batch, "n_space": args.n_space, "n_time": args.n_time,
+        "segments": len(groups), "segment_steps": [int(g.n_time) for g in groups],
+        "barrier": args.barrier, "reps": args.reps, "warmup": args.warmup,
+        "chain_ms": {"median": chain * 1e3, "min": min(res["chain"]["seconds"]) * 1e3,
+                     "max": max(res["chain"]["seconds"]) * 1e3,
+                     "host_calls_ms": statistics.median(res["chain"]["queued"]) * 1e3,
+                     "payoff_upload_call_ms": statistics.median(res["chain"]["upload"]) * 1e3},
+        "chain_host_payoff_ms": {"median": chain_host * 1e3,
+                                 "min": min(res["chain_host"]["seconds"]) * 1e3,
+                                 "max": max(res["chain_host"]["seconds"]) * 1e3,
+                                 "host_calls_ms":
+                                     statistics.median(res["chain_host"]["queued"]) * 1e3},
+        "plain_it_batch_dev_ms": {"median": plain_med * 1e3, "min": min(plain_t) * 1e3,
+                                  "max": max(plain_t) * 1e3},
+        "chain_over_plain": chain / plain_med,
+        "chain_host_over_chain": chain_host / chain,
+        "payoff_paths_bitwise_equal": bool(np.array_equal(prices, res["chain_host"]["prices"])),
+        "plan_seconds": t_plan,
+        "parity": facade_parity(p, jobs, prices),
+        "all_finite": bool(np.all(np.isfinite(prices))),
+        "price_range": [float(prices.min()), float(prices.max())],
+    }
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "american_ko_prices.npy"), prices)
+        line["dumped"] = {"american_ko_prices": list(prices.shape)}
+    print(json.dumps(line))
+    return 0 if line["parity"]["ok"] and line["all_finite"] else 3
+
+
+if __name__ == "__main__":
+    sys.exit(main())
