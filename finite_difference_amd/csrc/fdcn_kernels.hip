@@ -462,9 +462,20 @@ __host__ __device__ constexpr bool rec_form(int it, int w, int npt) {
 }
 
 // Sub-chains per lane (see "chunk decomposition" in fdcn_march).
+// FDCN_IT32_SUBCHAINS: the one-wave IT throughput variant at 32 nodes per
+// lane (config 2), overridable for A/B libraries only (1, 2 or 4; the
+// product build defines nothing).  Two since the homogeneous tables became
+// DPP operands: 10.19 ms per config-2 launch against 10.53 with four (one
+// job, medians of five); one chain measured 9.83 but is held back by the
+// committed-evidence checks (DESIGN sections 8 and 9).
+#ifndef FDCN_IT32_SUBCHAINS
+#define FDCN_IT32_SUBCHAINS 2
+#endif
+static_assert(FDCN_IT32_SUBCHAINS == 1 || FDCN_IT32_SUBCHAINS == 2 || FDCN_IT32_SUBCHAINS == 4,
+              "FDCN_IT32_SUBCHAINS: 1, 2 or 4");
 __host__ __device__ constexpr int sub_chains(int it, int w, int npt, int zg) {
   return (w == 1 && !(zg & 2))
-             ? (npt >= 48 ? 2 : ((it && npt == 32) ? 4 : 1))
+             ? (npt >= 48 ? 2 : ((it && npt == 32) ? FDCN_IT32_SUBCHAINS : 1))
              : ((npt % 4 == 0 && npt >= 16) ? 4 : ((npt % 2 == 0 && npt >= 8) ? 2 : 1));
 }
 
@@ -1008,7 +1019,13 @@ fdcn_march(KArgs A) {
   // with the current kernel (tools/gpu_ab.sh, one box, two runs each): the
   // IT NPT = 32 variant (config 2, two waves per SIMD) is now faster with
   // four: S = 1 11.39 ms, S = 2 11.38, S = 4 11.20; config 3 keeps one
-  // (5.91 against 6.04 with four).
+  // (5.91 against 6.04 with four).  Re-measured once the two-pass tables
+  // were DPP operands (a four-node update group then needs no table load,
+  // whatever S): S = 4 10.53 ms, S = 2 10.19, S = 1 9.83 -- the joins,
+  // carries, start values and fold FMAs of the extra sub-chains, 12 and 16
+  // VALU per step -- also with one wave per SIMD (B = 1100: 4.90 / 4.76 /
+  // 4.68 ms).  Config 2 runs two (DESIGN section 8 on one); the
+  // single-trade flavour keeps four.
   constexpr int S = sub_chains(IT, W, NPT, ZG);
   constexpr int M = NPT / S;
 
@@ -2293,7 +2310,8 @@ fdcn_march(KArgs A) {
       // itself (LDS returns in order: s_waitcnt lgkmcnt(2)); the
       // sched_barriers hold the loads where they are written.  Two groups
       // ahead measured 0.4 % slower at the same register count (DESIGN
-      // section 3).
+      // section 3); with two sub-chains at 247 registers it gained 0.13 ms,
+      // under three spreads (10.06 against 10.19 ms).
       constexpr int kGroups = NPT / 4;
       constexpr int kPkAhead = kGroups < 1 ? kGroups : 1;
       double pk[kGroups > 0 ? kGroups : 1][4];
