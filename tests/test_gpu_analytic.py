@@ -6,6 +6,8 @@ Tolerance: the device's erfc/exp/log/pow differ from glibc's in the last
 ulps, and the A-F factors subtract nearly equal terms, so agreement is
 |gpu - ref| <= 1e-11 |ref| + 1e-12 (the host engines match the reference to
 1e-12 relative, test_analytic.py).
+The edges, the overflow region, other m and the _dev entry points, against
+an 80-digit reference: test_gpu_analytic_precision.py.
 """
 import math
 
