@@ -10,6 +10,8 @@ import pytest
 
 from finite_difference_amd import capi
 from finite_difference_amd.engine import Engine, group_solves
+import march_cases as mc
+from march_cases import CASES, N_TIME_BLOCKS, PAIR_CASES, VARIANTS
 from plan_factory import random_solve
 
 pytestmark = pytest.mark.gpu
@@ -43,31 +45,22 @@ def _compare(solves, label, tol=TOL):
     return worst
 
 
-# (n_nodes, n_time, n_ranna): covers every W=1 NPT variant, short/phantom lanes,
-# inactive lanes, multi-wave variants, Rannacher on/off, n_ranna >= n_time.
-CASES = [
-    (6, 20, 2), (20, 37, 2), (67, 50, 0), (130, 64, 2), (257, 100, 2), (513, 200, 0),
-    (769, 120, 2), (1024, 150, 2), (1500, 90, 2), (2049, 128, 2), (2134, 60, 2),
-    (2600, 40, 2), (3000, 30, 2), (4097, 24, 2), (4265, 20, 2), (9000, 12, 2),
-    (300, 3, 5),
-    (5, 10, 2), (7, 30, 2), (8, 25, 0), (11, 40, 2),  # two-node chunks (NPT = 2)
-]
+# CASES (march_cases.py), (n_nodes, n_time, n_ranna): covers every W=1 NPT variant,
+# short/phantom lanes, inactive lanes, multi-wave variants, Rannacher on/off,
+# n_ranna >= n_time, two-node chunks.
 
 
 @pytest.mark.parametrize("n_nodes,n_time,n_ranna", CASES)
 def test_cn_ko_vs_oracle(n_nodes, n_time, n_ranna):
-    rng = np.random.default_rng(1000 + n_nodes)
-    B = 9
-    solves = [random_solve(rng, n_nodes, n_time, n_ranna, it=False, drop_top=(i % 2 == 0))
-              for i in range(B)]
+    solves = mc.cases_cn(n_nodes, n_time, n_ranna)
+    B = len(solves)
     _compare(solves, f"cn n={n_nodes} m={n_time} r={n_ranna} {capi.plan(n_nodes, False, B=B)}")
 
 
 @pytest.mark.parametrize("n_nodes,n_time,n_ranna", CASES)
 def test_it_vs_oracle(n_nodes, n_time, n_ranna):
-    rng = np.random.default_rng(2000 + n_nodes)
-    B = 7
-    solves = [random_solve(rng, n_nodes, n_time, n_ranna, it=True) for _ in range(B)]
+    solves = mc.cases_it(n_nodes, n_time, n_ranna)
+    B = len(solves)
     _compare(solves, f"it n={n_nodes} m={n_time} r={n_ranna} {capi.plan(n_nodes, True, B=B)}")
 
 
@@ -79,11 +72,7 @@ def test_it_vs_oracle(n_nodes, n_time, n_ranna):
 # tau += dt) from a non-zero tau0.  The default choice depends on the batch
 # size, so small test batches alone would not reach the throughput variants
 # the bench uses.
-VARIANTS = [(1, 2, 0), (1, 4, 0), (1, 8, 0), (1, 12, 0), (1, 16, 0), (1, 24, 0), (1, 32, 0), (1, 40, 0),
-            (1, 48, 0), (1, 64, 0), (2, 8, 0), (2, 16, 0), (2, 32, 0), (2, 40, 0), (4, 8, 0), (4, 16, 0),
-            (4, 24, 0), (4, 40, 0), (8, 8, 0), (8, 16, 0), (8, 40, 0), (16, 8, 0), (16, 24, 0),
-            (16, 40, 0), (1, 8, 1), (1, 16, 1), (1, 32, 1)]
-N_TIME_BLOCKS = 130
+# (VARIANTS and N_TIME_BLOCKS = 130: march_cases.py)
 
 
 @pytest.mark.parametrize("it", [False, True], ids=["cn", "it"])
@@ -95,14 +84,16 @@ def test_every_variant_vs_oracle(w, npt, fl, it, force_variant):
     plan = capi.plan(n_nodes, it, B=4)
     assert (plan["waves"], plan["npt"]) == (w, npt), plan
     assert capi.variant_name(n_nodes, it, B=4) == f"fdcn_march<{int(it)},{w},{npt},{2 * fl}>"
-    rng = np.random.default_rng(3000 + 7 * w + npt + 11 * fl + (1 if it else 0))
-    solves = [random_solve(rng, n_nodes, n_time, 2, it=it, drop_top=(i == 1)) for i in range(4)]
-    for i, s in enumerate(solves):
-        s.tau_accumulate = i % 2 == 1
-        s.tau0 = 0.0 if i < 2 else 0.037
+    solves = mc.forced_variant(w, npt, fl, it)
+    assert solves[0].n_nodes == n_nodes
     # these grids reach 40k nodes with few steps (dt sigma^2/dx^2 up to ~1e5, |fm|
     # within 1e-3 of 1): rounding in the O(n) recurrences of both solvers then
-    # grows with n, so the bound scales with n / 2048 above 2048 nodes
+    # grows with n, so the bound scales with n / 2048 above 2048 nodes.  (The
+    # oracle's own error against a long-double march of the same plan, measured
+    # in test_march_precision.py: up to 5.4e-12 at 2049 x 128, 3e-11 at 9000 x 12
+    # and 6.7e-10 at 40959 x 130, where this bound is 2e-9; the allowance is for
+    # the checker.  test_gpu_march_precision.py holds the same inputs to a bound
+    # measured per solve.)
     _compare(solves, f"{'it' if it else 'cn'} forced W={w} NPT={npt} F={fl} n={n_nodes} m={n_time}",
              tol=TOL * max(1.0, n_nodes / 2048))
 
@@ -113,8 +104,8 @@ def test_correction_table_in_workspace(it):
     whole 10k-node grid, its table no longer fits LDS, and the launch falls
     back to a ZG variant that keeps it in the global workspace."""
     n_nodes, n_time = 64 * 4 * 40 - 3 + 2, 3
-    rng = np.random.default_rng(77 + int(it))
-    solves = [random_solve(rng, n_nodes, n_time, 2, it=it) for _ in range(3)]
+    assert (n_nodes, n_time) == (mc.ZG_N_NODES, mc.ZG_N_TIME)
+    solves = mc.workspace_table(it)
     from finite_difference_amd.engine import pack
     g = pack(solves, list(range(3)))
     k_cap = capi.sm_extent(g.n_nodes, g.n_time, g.n_ranna, g.params)
@@ -161,24 +152,14 @@ def test_rec_form_every_step_knockout_vs_oracle(ko_lo, force_variant):
     step.  When the lower side covers the Sherman-Morrison lanes the kernel
     skips the correction on those steps (the projection overwrites it)."""
     force_variant(1, 64)
-    n_nodes, n_time = 4096, 96
-    rng = np.random.default_rng(4096 + ko_lo)
-    solves = []
-    for i in range(4):
-        s = random_solve(rng, n_nodes, n_time, 2, it=False, ko=False)
-        s.ko_lo, s.ko_hi = ko_lo, 3500 if i % 2 else 1 << 30
-        s.mon_steps = list(range(1, n_time + 1))
-        s.mon_rebates = [0.0 if i < 2 else 0.75] * n_time
-        solves.append(s)
+    solves = mc.rec_every_step_knockout(ko_lo)
+    n_nodes = solves[0].n_nodes
     assert capi.plan(n_nodes, False, B=4)["npt"] == 64
     _compare(solves, f"rec every-step KO ko_lo={ko_lo}")
 
 
-# The paired flavour (two scenarios per wave, lanes 0-31 and 32-63), forced:
-# full and partial lane use, an odd batch (the last wave's second scenario is
-# missing), per-scenario monitoring schedules and knock-out layouts, both
-# top-node layouts, accumulated tau.
-PAIR_CASES = [(8, 32 * 8 - 1, 5), (8, 32 * 8 + 1, 6), (8, 150, 4), (8, 97, 7), (8, 42, 1)]
+# PAIR_CASES (march_cases.py): the paired flavour (two scenarios per wave, lanes
+# 0-31 and 32-63), forced.
 
 
 @pytest.mark.parametrize("npt,n_nodes,B", PAIR_CASES,
@@ -187,12 +168,7 @@ def test_paired_variant_vs_oracle(npt, n_nodes, B, force_variant):
     force_variant(1, npt, 2)
     plan = capi.plan(n_nodes, False, B=B)
     assert (plan["waves"], plan["npt"], plan["scen_per_block"]) == (1, npt, 2), plan
-    rng = np.random.default_rng(5000 + npt + n_nodes + B)
-    solves = []
-    for i in range(B):
-        s = random_solve(rng, n_nodes, 60, 2, it=False, drop_top=(i % 3 == 0))
-        s.tau_accumulate = (i % 4 == 1)
-        solves.append(s)
+    solves = mc.paired(npt, n_nodes, B)
     _compare(solves, f"cn paired NPT={npt} n={n_nodes} B={B}")
 
 
@@ -200,15 +176,7 @@ def test_paired_every_step_knockout_vs_oracle(force_variant):
     """Knock-out schedules that differ between the two scenarios of a wave:
     every step on one, sparse on the other, rebates on both sides."""
     force_variant(1, 8, 2)
-    n_nodes, n_time = 256, 80
-    rng = np.random.default_rng(99)
-    solves = []
-    for i in range(6):
-        s = random_solve(rng, n_nodes, n_time, 2, it=False, ko=False)
-        s.ko_lo, s.ko_hi = (10 + 9 * i, 225 - 3 * i) if i % 2 else (-1, 175)
-        s.mon_steps = list(range(1, n_time + 1)) if i % 2 == 0 else [5, 17, 18, 60, n_time]
-        s.mon_rebates = [0.5 * (i % 3)] * len(s.mon_steps)
-        solves.append(s)
+    solves = mc.paired_mixed_schedules()
     _compare(solves, "cn paired, mixed knock-out schedules")
 
 
@@ -230,26 +198,10 @@ def test_split_two_pass_every_step_knockout_vs_oracle(ko_lo, force_variant):
     boundary terms after a knock-out (ko_prev) and the folded
     Sherman-Morrison correction under a projection that covers its lanes."""
     force_variant(1, 16)
-    n_nodes, n_time = 1024, 150
-    rng = np.random.default_rng(1600 + ko_lo)
-    solves = []
-    for i in range(6):
-        s = random_solve(rng, n_nodes, n_time, 2, it=False, ko=False, drop_top=(i % 2 == 0))
-        s.ko_lo, s.ko_hi = ko_lo, (900 if i % 3 else 1 << 30)
-        s.mon_steps = list(range(1, n_time + 1)) if i < 3 else list(range(2, n_time + 1, 7))
-        s.mon_rebates = [0.0 if i % 2 else 1.25] * len(s.mon_steps)
-        s.tau_accumulate = i % 2 == 1
-        solves.append(s)
+    solves = mc.split_two_pass_knockout(ko_lo)
+    n_nodes = solves[0].n_nodes
     assert capi.variant_name(n_nodes, False, B=6) == "fdcn_march<0,1,16,0>"
     _compare(solves, f"split two-pass every-step KO ko_lo={ko_lo}")
-
-
-def _fm(a, c, bc, dt, theta):
-    """The converged forward multiplier fm = -A_L / r of A = I - theta dt L
-    (r: the larger root of r^2 - A_C r + A_L A_U = 0), as the kernel's phase."""
-    AL, AC, AU = -theta * dt * a, 1.0 - theta * dt * bc, -theta * dt * c
-    r = 0.5 * (AC + np.sqrt(AC * AC - 4.0 * AL * AU))
-    return -AL / r
 
 
 @pytest.mark.parametrize("n_nodes", [4096, 4097, 3000], ids=["short2", "full", "npt48"])
@@ -261,24 +213,10 @@ def test_rec_form_half_chunk_aggregates_vs_oracle(n_nodes, force_variant):
     that adds the other halves): both paths in one march, with a knock-out
     on every step, short lanes (4096 nodes: two), a full layout (4097) and
     the 48-node chunks (3000 nodes)."""
-    npt = 48 if n_nodes == 3000 else 64
+    npt = mc.half_chunk_npt(n_nodes)
     force_variant(1, npt)
-    rng = np.random.default_rng(77 + n_nodes)
-    solves = []
-    for i in range(6):
-        s = random_solve(rng, n_nodes, 80, 2, it=False, ko=False)
-        a, c, bc = s.coeffs
-        # dt a in a band where the CN phase's |fm|^(NPT/2) is < 1e-18 and the
-        # Rannacher phase's is not
-        s.dt = ((0.6 + 0.04 * i) if npt == 64 else (0.3 + 0.03 * i)) / a
-        fm_cn, fm_r = _fm(a, c, bc, s.dt, 0.5), _fm(a, c, bc, s.dt, 1.0)
-        bm_cn = _fm(c, a, bc, s.dt, 0.5)
-        assert abs(fm_cn) ** (npt // 2) < 1e-18 and abs(bm_cn) ** (npt // 2) < 1e-18, (fm_cn, bm_cn)
-        assert abs(fm_r) ** (npt // 2) > 1e-18, fm_r  # the Rannacher steps take the branch
-        s.ko_lo, s.ko_hi = int(rng.integers(-1, 600)), int(rng.integers(n_nodes - 700, n_nodes + 2))
-        s.mon_steps = list(range(1, s.n_time + 1))
-        s.mon_rebates = [0.0 if i % 2 else 0.4] * s.n_time
-        solves.append(s)
+    # the builder asserts the |fm|^(NPT/2) band of both phases on every solve
+    solves = mc.half_chunk_aggregates(n_nodes)
     assert capi.plan(n_nodes, False, B=6)["npt"] == npt
     _compare(solves, f"rec half-chunk aggregates n={n_nodes}")
 
@@ -292,17 +230,9 @@ def test_one_sided_table_batch_vs_oracle(n_nodes, npt):
     edge node or not, sparse and every-step monitoring, accumulated tau --
     the raw values kept only for the steps after an edge knock-out, every
     node against the oracle."""
-    rng = np.random.default_rng(777 + n_nodes)
-    B = 300
-    solves = []
-    for i in range(B):
-        s = random_solve(rng, n_nodes, 150, 2, it=False, drop_top=(i % 2 == 0))
-        s.tau_accumulate = i % 5 == 1
-        if i % 7 == 3:  # a knock-out on every step reaching node 0 / the last node
-            s.ko_lo, s.ko_hi = int(rng.integers(0, 40)), n_nodes - int(rng.integers(1, 40))
-            s.mon_steps = list(range(1, 151))
-            s.mon_rebates = [0.25] * 150
-        solves.append(s)
+    solves = mc.one_sided_table(n_nodes)
+    B = len(solves)
+    assert B == 300
     plan = capi.plan(n_nodes, False, B=B)
     assert (plan["waves"], plan["npt"]) == (1, npt), plan
     _compare(solves, f"one-sided table n={n_nodes} B={B}", tol=TOL * max(1.0, n_nodes / 2048))
@@ -320,11 +250,5 @@ def test_it_throughput_batch_vs_oracle(n_nodes, B, n_ranna, variant):
     ran a one-sided-table build of these variants through it, measured and
     not kept: profiles/r06/config2_tab1/.)"""
     assert capi.variant_name(n_nodes, True, B=B) == variant
-    rng = np.random.default_rng(2049 + n_nodes + B + n_ranna)
-    solves = []
-    for i in range(B):
-        s = random_solve(rng, n_nodes, 150, n_ranna, it=True)
-        s.tau_accumulate = i % 5 == 1
-        s.tau0 = 0.0 if i % 3 else 0.021
-        solves.append(s)
+    solves = mc.it_throughput(n_nodes, B, n_ranna)
     _compare(solves, f"it throughput batch n={n_nodes} B={B} r={n_ranna}")
