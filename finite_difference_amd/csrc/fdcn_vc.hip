@@ -175,8 +175,10 @@ __device__ __forceinline__ size_t ws_scen(const VcArgs& A) {
 // group up to it, times the product of all earlier groups (carried), so
 // each lane has c*_{i-1} for its row and takes the reference's step from
 // it.  The recurrence contracts (|dc*_i / dc*_{i-1}| = |sub_i sup_i| /
-// beta_i^2 < 1 on these diagonally dominant rows), so the pivots equal the
-// serial sweep's to rounding.
+// beta_i^2 < 1 on these diagonally dominant rows), but the product loses
+// 1 / (1 - contraction) of its precision, so the scan's c* takes one Newton
+// step (a second, affine lane scan, factor_rows) before it is used: then
+// the pivots equal the serial sweep's to the sweep's own rounding.
 // ---------------------------------------------------------------------------
 __host__ __device__ double row_ratio(const double* P, int n, int i) {
   const double sub = P[i], sup = P[2 * n + i], ae = P[3 * n + i], ce = P[5 * n + i];
@@ -282,6 +284,8 @@ __device__ __forceinline__ FactorClass factor_rows(const double* P, int n, int s
   }
   FactorClass fc{0, 0x7fffffff, -1};
   M2 carry{1.0, 0.0, 0.0, 1.0};  // the product of every earlier group's matrices
+  double scarry = 0.0;           // the scan's c* of the last earlier row,
+  double dcarry = 0.0;           // and its Newton correction
   for (int base = 0; base < n; base += 64) {
     const int i = base + lane;
     const bool row = i < n;
@@ -293,14 +297,38 @@ __device__ __forceinline__ FactorClass factor_rows(const double* P, int n, int s
       if (lane >= d) T = mnorm(mmul(T, X));
     }
     const M2 Pi = mnorm(mmul(T, carry));  // rows 0..i
-    // c* of row i-1: the previous lane's product, or the carry for lane 0,
-    // applied to (p, q) = (0, 1)
-    double pb = shfl_d(Pi.b, lane - 1), qb = shfl_d(Pi.d, lane - 1);
-    if (lane == 0) {
-      pb = carry.b;
-      qb = carry.d;
-    }
+    // the scan's c* of row i, s_i = p / q of the product applied to (0, 1),
+    // and of row i-1: the previous lane's, or the carry's for lane 0
+    const double si = Pi.b / Pi.d;
+    double sprev = shfl_d(si, lane - 1);
+    if (lane == 0) sprev = scarry;
+    scarry = shfl_d(si, 63);
     carry = M2{shfl_d(Pi.a, 63), shfl_d(Pi.b, 63), shfl_d(Pi.c, 63), shfl_d(Pi.d, 63)};
+    // One Newton step on the scan's values.  The entries of a long product
+    // are differences of its two eigen-directions, so where the recurrence
+    // contracts weakly (kappa_i = sub_i sup_i / beta_i^2 near 1: the high-S
+    // rows of a fine grid) s_i is off by ~10 u / (1 - kappa), up to 3 000 u
+    // at 16 385 nodes, thirty times the serial sweep's own error.  With
+    // c*_i = s_i + d_i the sweep's step F_i(c) = sup_i / (main_i - sub_i c)
+    // linearises to d_i = r_i + kappa_i d_{i-1}, r_i = F_i(s_{i-1}) - s_i
+    // (the residual of the scan, exact to a rounding of F_i), an affine
+    // recurrence with the sweep's own conditioning: one more lane scan, its
+    // carry d of the last row handed to the next group.  d^2 ~ 1e-25.
+    const double bs = m - sb * sprev;
+    const double rb = __builtin_amdgcn_rcp(bs);  // kappa scales d ~ 1e-13: v_rcp_f64 is ample
+    double kap = row ? (sb * sp) * (rb * rb) : 1.0;
+    double res = row ? sp / bs - si : 0.0;
+    for (int d = 1; d < 64; d <<= 1) {
+      const double ko = shfl_d(kap, lane - d), ro = shfl_d(res, lane - d);
+      if (lane >= d) {
+        res = fma(kap, ro, res);
+        kap *= ko;
+      }
+    }
+    const double di = fma(kap, dcarry, res);  // c*_i - s_i
+    double dprev = shfl_d(di, lane - 1);
+    if (lane == 0) dprev = dcarry;
+    dcarry = shfl_d(di, 63);
     const bool interior = row && i > 0 && i < n - 1;
     // kFast: this group's exceptional rows (residual not exactly zero)
     double ra = 0.0, rc = 0.0;
@@ -321,7 +349,7 @@ __device__ __forceinline__ FactorClass factor_rows(const double* P, int n, int s
       }
     }
     if (!row) continue;
-    const double cprev = i > 0 ? pb / qb : 0.0;
+    const double cprev = i > 0 ? sprev + dprev : 0.0;
     const double beta = (i == 0) ? m : m - sb * cprev;
     const double g = 1.0 / beta;
     const double cs = (i < n - 1) ? sp / beta : 0.0;

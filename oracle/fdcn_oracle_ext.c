@@ -27,6 +27,12 @@
  *   ... -DEXT_RECOVERY in addition
  *       the same with the kernels' split / recovery form of the Crank-Nicolson
  *       right-hand side (see plan_solve_one).
+ *
+ * oracle_ext_vc_batch (every build): section 3 of fdcn_oracle.c, the spot-space
+ * march with per-row coefficients, over REAL; its `order` argument selects the
+ * Thomas march (0, bit-identical to oracle_vc_batch in the f64 build) or the
+ * sequential restatement of csrc/fdcn_vc.hip's ordering (1 stencil form,
+ * 2 pointwise form), see vc_solve_one.
  */
 #include <float.h>
 #include <math.h>
@@ -273,6 +279,190 @@ int oracle_ext_it_batch(int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ra
                         int32_t nthreads) {
   return plan_batch(1, B, n_nodes, n_time, n_ranna, params, iparams, v_init, payoff, NULL,
                     NULL, out_hi, out_lo, nthreads);
+}
+
+/* ---------------------------------------------------------------------- */
+/* spot-space CN with per-row coefficients: vc_solve_one of fdcn_oracle.c  */
+/* over REAL (order 0), on the plan arrays of fdcn_vc_batch.              */
+/*                                                                        */
+/* order 1 / 2: the ordering of csrc/fdcn_vc.hip restated sequentially,   */
+/* with no scans.  Per phase the Thomas pivots beta_i are taken once and  */
+/* the rows stored scaled, g = 1/beta, f = -sub g, e = -sup/beta, each    */
+/* rounded once; g is folded into the explicit rows; the Dirichlet values */
+/* enter as the carries g_0 lo and g_N hi of the two recurrences.         */
+/*   1  stencil form:   d_i = (A V_{i-1} + B V_i + C V_{i+1}) + f_i d_{i-1} */
+/*                      x_i = d_i + e_i x_{i+1},  A = a g, B = b g, C = c g */
+/*   2  pointwise form: alpha from the candidate row (n/2, 1, n-2) with   */
+/*      the fewest residual rows; B = g (b - alpha main); residual rows   */
+/*      add g (a - alpha sub) V_{i-1} + g (c - alpha sup) V_{i+1}; the    */
+/*      carries are g_0 lo - alpha V_0 and g_N hi - alpha V_N; x = alpha  */
+/*      V + u.  (The kernel keeps at most two residual rows and sends the */
+/*      rest to the stencil form; this restatement takes any number.)     */
+/* Products written a * b + c contract under -ffp-contract=fast as the    */
+/* kernels' fma() calls do.  In exact arithmetic all three are the same   */
+/* solve.                                                                 */
+/* ---------------------------------------------------------------------- */
+static REAL vc_row_ratio(const double* P, int n, int i) {
+  const REAL sub = R(P[i]), sup = R(P[2 * n + i]);
+  if (sub != R(0.0)) return R(P[3 * n + i]) / sub;
+  return sup != R(0.0) ? R(P[5 * n + i]) / sup : R(0.0);
+}
+
+/* per phase, scaled rows: cA, cB, cC, cf, ce of n each, then g (n); *alpha */
+static void vc_factor_phase(int order, int n, const double* P, REAL* C, REAL* alpha) {
+  const double *sub = P, *mn = P + n, *sup = P + 2 * n;
+  const double *ae = P + 3 * n, *be = P + 4 * n, *ce = P + 5 * n;
+  REAL *cA = C, *cB = C + n, *cC = C + 2 * n, *cf = C + 3 * n, *cE = C + 4 * n, *g = C + 5 * n;
+  REAL al = R(0.0);
+  if (order == 2) {
+    const int cand[3] = {n / 2, 1, n - 2};
+    int best = n + 1;
+    for (int k = 0; k < 3; ++k) {
+      const REAL a_k = vc_row_ratio(P, n, cand[k]);
+      int cnt = 0;
+      for (int i = 1; i < n - 1; ++i)
+        if (R(ae[i]) - a_k * R(sub[i]) != R(0.0) || R(ce[i]) - a_k * R(sup[i]) != R(0.0)) ++cnt;
+      if (cnt < best) {
+        best = cnt;
+        al = a_k;
+      }
+    }
+  }
+  *alpha = al;
+  REAL cs = R(0.0);
+  for (int i = 0; i < n; ++i) {
+    const REAL beta = i == 0 ? R(mn[0]) : R(mn[i]) - R(sub[i]) * cs;
+    g[i] = R(1.0) / beta;
+    cs = i < n - 1 ? R(sup[i]) / beta : R(0.0);
+    const int interior = i > 0 && i < n - 1;
+    if (order == 2) {
+      cA[i] = interior ? g[i] * (R(ae[i]) - al * R(sub[i])) : R(0.0);
+      cB[i] = interior ? g[i] * (R(be[i]) - al * R(mn[i])) : R(0.0);
+      cC[i] = interior ? g[i] * (R(ce[i]) - al * R(sup[i])) : R(0.0);
+    } else {
+      cA[i] = interior ? R(ae[i]) * g[i] : R(0.0);
+      cB[i] = interior ? R(be[i]) * g[i] : R(0.0);
+      cC[i] = interior ? R(ce[i]) * g[i] : R(0.0);
+    }
+    cf[i] = interior ? -R(sub[i]) * g[i] : R(0.0);
+    cE[i] = interior ? -cs : R(0.0);
+  }
+}
+
+static void vc_solve_one(int order, int n, int n_time, int n_ranna, const double* D,
+                         const double* bnd, const double* v_init, const int32_t* I,
+                         const int32_t* mon_step, const double* mon_rebate, double* out_hi,
+                         double* out_lo, REAL* work) {
+  REAL* V = work;
+  REAL* rhs = V + n;
+  REAL* cs = rhs + n;
+  REAL* ds = cs + n;
+  REAL* x = ds + n;
+  REAL* fac = x + n; /* order 1 / 2: two phases of 6 n scaled rows */
+  REAL alpha[2] = {R(0.0), R(0.0)};
+  for (int j = 0; j < n; ++j) V[j] = R(v_init[j]);
+  if (order) {
+    if (n_ranna > 0) vc_factor_phase(order, n, D, fac, &alpha[0]);
+    if (n_ranna < n_time)
+      vc_factor_phase(order, n, D + (size_t)FDCN_VC_NDIAG * n, fac + 6 * (size_t)n, &alpha[1]);
+  }
+  int mon_pos = I[FDCN_I_MON_START];
+  const int mon_end = mon_pos + I[FDCN_I_MON_COUNT];
+  const int ko_lo = I[FDCN_I_KO_LO], ko_hi = I[FDCN_I_KO_HI];
+  for (int m = 0; m < n_time; ++m) {
+    const int ph = m < n_ranna ? 0 : 1;
+    if (order) {
+      const REAL* C = fac + (size_t)ph * 6 * n;
+      const REAL *cA = C, *cB = C + n, *cC = C + 2 * n, *cf = C + 3 * n, *cE = C + 4 * n,
+                 *g = C + 5 * n;
+      const REAL al = alpha[ph];
+      const REAL x0 = g[0] * R(bnd[2 * (size_t)m]), xN = g[n - 1] * R(bnd[2 * (size_t)m + 1]);
+      if (order == 2) {
+        for (int i = 1; i < n - 1; ++i) {
+          rhs[i] = cB[i] * V[i];
+          if (cA[i] != R(0.0) || cC[i] != R(0.0))
+            rhs[i] = cA[i] * V[i - 1] + (cC[i] * V[i + 1] + rhs[i]);
+        }
+        ds[0] = -al * V[0] + x0;
+        x[n - 1] = -al * V[n - 1] + xN;
+      } else {
+        for (int i = 1; i < n - 1; ++i)
+          rhs[i] = cC[i] * V[i + 1] + (cB[i] * V[i] + cA[i] * V[i - 1]);
+        ds[0] = x0;
+        x[n - 1] = xN;
+      }
+      for (int i = 1; i < n - 1; ++i) ds[i] = cf[i] * ds[i - 1] + rhs[i];
+      for (int i = n - 2; i >= 1; --i) x[i] = cE[i] * x[i + 1] + ds[i];
+      if (order == 2)
+        for (int i = 1; i < n - 1; ++i) x[i] = al * V[i] + x[i];
+      x[0] = x0;
+      x[n - 1] = xN;
+    } else {
+      const double* P = D + (size_t)ph * FDCN_VC_NDIAG * n;
+      const double *sub = P, *main_ = P + n, *sup = P + 2 * n;
+      const double *ae = P + 3 * n, *be = P + 4 * n, *ce = P + 5 * n;
+      rhs[0] = R(bnd[2 * (size_t)m]);
+      rhs[n - 1] = R(bnd[2 * (size_t)m + 1]);
+      for (int i = 1; i < n - 1; ++i)
+        rhs[i] = R(ae[i]) * V[i - 1] + R(be[i]) * V[i] + R(ce[i]) * V[i + 1];
+      REAL beta = R(main_[0]);
+      cs[0] = R(sup[0]) / beta;
+      ds[0] = rhs[0] / beta;
+      for (int i = 1; i < n; ++i) {
+        beta = R(main_[i]) - R(sub[i]) * cs[i - 1];
+        cs[i] = (i < n - 1) ? R(sup[i]) / beta : R(0.0);
+        ds[i] = (rhs[i] - R(sub[i]) * ds[i - 1]) / beta;
+      }
+      x[n - 1] = ds[n - 1];
+      for (int i = n - 2; i >= 0; --i) x[i] = ds[i] - cs[i] * x[i + 1];
+    }
+    memcpy(V, x, sizeof(REAL) * (size_t)n);
+    if (mon_pos < mon_end && mon_step[mon_pos] == m + 1) {
+      const REAL reb = R(mon_rebate[mon_pos]);
+      for (int j = 0; j < n; ++j)
+        if (j <= ko_lo || j >= ko_hi) V[j] = reb;
+      ++mon_pos;
+    }
+    while (mon_pos < mon_end && mon_step[mon_pos] <= m + 1) ++mon_pos;
+  }
+  for (int j = 0; j < n; ++j) {
+    const double h = (double)V[j];
+    out_hi[j] = h;
+    out_lo[j] = (double)(V[j] - R(h));
+  }
+}
+
+int oracle_ext_vc_batch(int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
+                        const double* diag, const double* bnd, const double* v_init,
+                        const int32_t* iparams, int32_t n_mon, const int32_t* mon_step,
+                        const double* mon_rebate, double* out_hi, double* out_lo,
+                        int32_t order, int32_t nthreads) {
+  (void)n_mon;
+  if (B < 0 || n_nodes < 3 || n_time < 0 || order < 0 || order > 2) return FDCN_EINVAL;
+  int err = 0;
+#ifdef _OPENMP
+  if (nthreads < 1) nthreads = 1;
+#pragma omp parallel num_threads(nthreads)
+#endif
+  {
+    REAL* work = (REAL*)malloc(sizeof(REAL) * 17 * (size_t)n_nodes);
+    if (!work) {
+      err = FDCN_ENOMEM;
+    } else {
+#ifdef _OPENMP
+#pragma omp for schedule(dynamic, 1)
+#endif
+      for (int32_t b = 0; b < B; ++b)
+        vc_solve_one(order, n_nodes, n_time, n_ranna,
+                     diag + (size_t)b * 2 * FDCN_VC_NDIAG * n_nodes,
+                     bnd + (size_t)b * 2 * (size_t)n_time, v_init + (size_t)b * n_nodes,
+                     iparams + (size_t)b * FDCN_NIPARAM, mon_step, mon_rebate,
+                     out_hi + (size_t)b * n_nodes, out_lo + (size_t)b * n_nodes, work);
+      free(work);
+    }
+  }
+  (void)nthreads;
+  return err;
 }
 
 /* significand bits of REAL (53, 64 on x86, 113) */

@@ -75,6 +75,9 @@ def lib(kind: str) -> ctypes.CDLL:
         L.oracle_ext_it_batch.restype = ctypes.c_int
         L.oracle_ext_it_batch.argtypes = [_I32, _I32, _I32, _I32, _PD, _PI32, _PD, _PD, _PD, _PD,
                                           _I32]
+        L.oracle_ext_vc_batch.restype = ctypes.c_int
+        L.oracle_ext_vc_batch.argtypes = [_I32, _I32, _I32, _I32, _PD, _PD, _PD, _PI32, _I32,
+                                          _PI32, _PD, _PD, _PD, _I32, _I32]
         L.oracle_ext_mant_dig.restype = ctypes.c_int
         _libs[kind] = L
     return L
@@ -98,6 +101,33 @@ def cn_batch(kind: str, n_nodes: int, n_time: int, n_ranna: int, params, iparams
                                        int(nthreads))
     if rc != 0:
         raise RuntimeError(f"oracle_ext_cn_batch[{kind}] failed ({rc})")
+    return hi, lo
+
+
+VC_THOMAS, VC_KERNEL_STENCIL, VC_KERNEL_POINTWISE = 0, 1, 2
+
+
+def vc_batch(kind: str, n_nodes: int, n_time: int, n_ranna: int, diag, bnd, v_init, iparams,
+             mon_step, mon_rebate, nthreads: int = 1,
+             order: int = VC_THOMAS) -> Tuple[np.ndarray, np.ndarray]:
+    """The spot-space per-row march on the fdcn_vc_batch plan (oracle.vc_batch's
+    arguments) in the arithmetic `kind` ("f64", "f64fma", "ld", "quad").
+    order: the Thomas march, or the sequential restatement of fdcn_vc.hip's
+    ordering in its stencil / pointwise form."""
+    D, Bd, V, I = _f64(diag), _f64(bnd), _f64(v_init), _i32(iparams)
+    B = V.shape[0]
+    ms = _i32(mon_step) if len(mon_step) else _i32([0])
+    mr = _f64(mon_rebate) if len(mon_rebate) else _f64([0.0])
+    if Bd.size == 0:
+        Bd = _f64([0.0, 0.0])
+    hi = np.empty((B, n_nodes), dtype=np.float64)
+    lo = np.empty((B, n_nodes), dtype=np.float64)
+    rc = lib(kind).oracle_ext_vc_batch(B, n_nodes, n_time, n_ranna, _pd(D), _pd(Bd), _pd(V),
+                                       I.ctypes.data_as(_PI32), len(mon_step),
+                                       ms.ctypes.data_as(_PI32), _pd(mr), _pd(hi), _pd(lo),
+                                       int(order), int(nthreads))
+    if rc != 0:
+        raise RuntimeError(f"oracle_ext_vc_batch[{kind}] failed ({rc})")
     return hi, lo
 
 

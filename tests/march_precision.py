@@ -41,17 +41,33 @@ values.  Nothing here is taken from a kernel's output.
 
 Errors are (V - hi) - lo in fp64 with V_ext = hi + lo, so knocked-out nodes
 and exact zeros compare equal.
+
+The spot-space per-row march (engine.VcGroup, csrc/fdcn_vc.hip) goes through
+the same Yardstick with the same constants.  Its three realisations are the
+literal march of oracle_vc_batch, the same contracted, and the mirrored plan
+(sub <-> sup and a <-> c swapped, every row array reversed, the bnd columns
+swapped, ko_lo / ko_hi -> n-1-ko_hi / n-1-ko_lo, v_init reversed, the result
+reversed back).  The 2e-18 n_time vmax term is 0 for these groups: fdcn_vc.hip
+truncates nothing.  Its factor kernel finds the pivots by an exact projective
+product scan (powers of two only rescale it), the march's two recurrences are
+exact affine scans over all lanes and waves with the Dirichlet values as
+carry-ins, and no cut-off constant appears in the file -- read against the
+source: the only literals in its arithmetic are 0 and 1.  Its own ordering
+(rows stored scaled by 1 / pivot, rounded once per phase; the pointwise form
+x = alpha V + u) is restated sequentially by oracle_ext.vc_batch(order=1, 2):
+KERNEL_STENCIL and KERNEL_POINTWISE below, a fourth realisation only for the
+groups of vc_cases.KERNEL_ORDER_GROUPS and never part of leave-one-out.
 """
 from __future__ import annotations
 
 import dataclasses
 from dataclasses import dataclass
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
 from finite_difference_amd import capi
-from finite_difference_amd.engine import Group
+from finite_difference_amd.engine import Group, VcGroup
 
 U = 2.0 ** -53
 FACTOR = 8.0
@@ -59,14 +75,29 @@ TAIL_REL = 1e-3
 SERIES_CUT = 2e-18
 REALISATIONS = ("f64", "f64fma", "mirror")
 KERNEL_ORDER = "kernel_order"
+KERNEL_STENCIL, KERNEL_POINTWISE = "kernel_stencil", "kernel_pointwise"  # VcGroup only
+_VC_ORDER = {KERNEL_STENCIL: 1, KERNEL_POINTWISE: 2}
 NTHREADS = 8
 OLD_TOL = 1e-10
 
 
-def mirror_group(g: Group) -> Group:
+def _mirror_vc(g: VcGroup) -> VcGroup:
+    n = g.n_nodes
+    I = g.iparams.copy()
+    I[:, capi.I_KO_LO] = n - 1 - g.iparams[:, capi.I_KO_HI]
+    I[:, capi.I_KO_HI] = n - 1 - g.iparams[:, capi.I_KO_LO]
+    D = g.diag[:, :, [2, 1, 0, 5, 4, 3], ::-1]  # sub <-> sup, a <-> c, rows reversed
+    return dataclasses.replace(
+        g, diag=np.ascontiguousarray(D), bnd=np.ascontiguousarray(g.bnd[:, :, ::-1]),
+        iparams=I, v_init=np.ascontiguousarray(g.v_init[:, ::-1]))
+
+
+def mirror_group(g: Union[Group, VcGroup]) -> Union[Group, VcGroup]:
     """The same marches with the node order reversed: a <-> c, the boundary
     blocks and forms swapped, ko_lo / ko_hi -> n-1-ko_hi / n-1-ko_lo, v_init
     and the payoff reversed.  The monitor schedule is unchanged."""
+    if isinstance(g, VcGroup):
+        return _mirror_vc(g)
     n = g.n_nodes
     P = g.params.copy()
     I = g.iparams.copy()
@@ -81,9 +112,13 @@ def mirror_group(g: Group) -> Group:
         payoff=None if g.payoff is None else np.ascontiguousarray(g.payoff[:, ::-1]))
 
 
-def march(kind: str, g: Group) -> Tuple[np.ndarray, np.ndarray]:
-    """(hi, lo) of the group's marches in the arithmetic `kind` of oracle_ext."""
+def march(kind: str, g: Union[Group, VcGroup], order: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """(hi, lo) of the group's marches in the arithmetic `kind` of oracle_ext
+    (order: oracle_ext.vc_batch's, VcGroup only)."""
     from oracle import oracle_ext
+    if isinstance(g, VcGroup):
+        return oracle_ext.vc_batch(kind, g.n_nodes, g.n_time, g.n_ranna, g.diag, g.bnd, g.v_init,
+                                   g.iparams, g.mon_step, g.mon_rebate, NTHREADS, order)
     if g.it:
         return oracle_ext.it_batch(kind, g.n_nodes, g.n_time, g.n_ranna, g.params, g.iparams,
                                    g.v_init, g.payoff, NTHREADS)
@@ -99,6 +134,8 @@ def march_mirrored(kind: str, g: Group) -> Tuple[np.ndarray, np.ndarray]:
 def realise(name: str, g: Group) -> np.ndarray:
     if name == "mirror":
         return march_mirrored("f64", g)[0]
+    if name in _VC_ORDER:
+        return march("f64fma", g, _VC_ORDER[name])[0]
     if name == KERNEL_ORDER:
         return march("f64rec", g)[0]
     return march(name, g)[0]
@@ -115,7 +152,7 @@ def _ratio(err: np.ndarray, bound: np.ndarray) -> np.ndarray:
 
 @dataclass
 class Yardstick:
-    g: Group
+    g: Union[Group, VcGroup]
     hi: np.ndarray                 # [B, n]  (double) V_ext
     lo: np.ndarray                 # [B, n]  (double)(V_ext - hi)
     real: Dict[str, np.ndarray]    # the fp64 realisations, [B, n] each
@@ -143,8 +180,9 @@ class Yardstick:
         N, NT = self.noise(exclude)
         vmax = self.vmax
         b_max = FACTOR * np.maximum(N, 2.0 * U * vmax)
+        cut = 0.0 if isinstance(self.g, VcGroup) else SERIES_CUT  # fdcn_vc truncates nothing
         b_tail = (FACTOR * np.maximum(NT, 2.0 * U * TAIL_REL * vmax)
-                  + SERIES_CUT * self.g.n_time * vmax)
+                  + cut * self.g.n_time * vmax)
         return b_max, b_tail
 
     def ratios(self, V: np.ndarray, exclude: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray]:
@@ -176,7 +214,7 @@ class Yardstick:
         return w_max, w_tail
 
 
-def yardstick(g: Group, realisations: Sequence[str] = REALISATIONS) -> Yardstick:
+def yardstick(g: Union[Group, VcGroup], realisations: Sequence[str] = REALISATIONS) -> Yardstick:
     hi, lo = march("ld", g)
     return Yardstick(g, hi, lo, {k: realise(k, g) for k in realisations})
 

@@ -21,24 +21,9 @@ import numpy as np
 import pytest
 
 from backends import oracle_engine
-from conftest import load_golden
 from finite_difference_amd.engine import Engine
-from finite_difference_amd.spot_barrier import DiscreteBarrierFDMPricer2
-
-GOLD = load_golden("spot_cases.json")
-V0 = dt.date.fromisoformat(GOLD["valuation"])
-V1 = dt.date.fromisoformat(GOLD["maturity"])
-
-
-def make(inp, engine, **extra):
-    kw = dict(inp)
-    kw.pop("name", None)
-    if "monitoring_dates" in kw:
-        kw["monitoring_dates"] = [dt.date.fromisoformat(d) for d in kw["monitoring_dates"]]
-    if "dividends" in kw:
-        kw["dividends"] = [(dt.date.fromisoformat(d), a) for d, a in kw["dividends"]]
-    kw.update(extra)
-    return DiscreteBarrierFDMPricer2(valuation_date=V0, maturity_date=V1, engine=engine, **kw)
+from vc_cases import (GOLD, V0, _random_rows, _vanilla_solve, _with_exceptional_rows,  # noqa: F401
+                      exceptional_positions, factor_scan, make, mixed_forms, split_phase_rows)
 
 
 @pytest.mark.parametrize("case", GOLD["cases"], ids=lambda c: c["name"])
@@ -220,30 +205,6 @@ def test_spot_dev_entry_skips_repeated_monitor_steps(n):
     assert got[0][0] == 0.25 * 9 and got[1][-1] == 0.25 * 7
 
 
-def _vanilla_solve(n, m, opt="put"):
-    inp = dict(spot=100.0, strike=100.0, volatility=0.25, option_type=opt, barrier_type="none",
-               flat_rate_nacc=0.05, num_space_nodes=n - 1, num_time_steps=m)
-    return make(inp, None, explicit_sign="corrected")._grid_solves()[2][0]
-
-
-def _with_exceptional_rows(sv, i1, ko=True):
-    """A copy of a vanilla spot-space solve whose CN-phase explicit rows i1
-    and i1 + 1 are no longer -1 times the implicit ones (as the reference's
-    one-sided barrier rows are not, :388-410) -- perturbed by 0.1 %, not
-    flipped: a flipped row in the middle of the grid makes the march grow
-    like 1e53 in 60 steps, and the comparison would measure that growth --
-    with a knock-out below node n/4 and above 3n/4 on every fifth step."""
-    import dataclasses
-    D = sv.diag.copy()
-    for i in (i1, i1 + 1):
-        D[1, 3, i] *= 1.001
-        D[1, 5, i] *= 0.999
-    n = sv.n_nodes
-    kw = dict(ko_lo=n // 4, ko_hi=3 * n // 4, mon_steps=list(range(5, sv.n_time + 1, 5)),
-              mon_rebates=[0.5] * len(range(5, sv.n_time + 1, 5))) if ko else {}
-    return dataclasses.replace(sv, diag=D, **kw)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("w,npt,n", [(1, 16, 1025), (1, 8, 513), (1, 4, 257), (4, 16, 4097),
                                      (4, 8, 2049), (16, 4, 4096), (1, 16, 1000), (1, 10, 601),
@@ -256,12 +217,7 @@ def test_pointwise_exceptional_rows_at_every_slot_position(w, npt, n):
     pinned variant, each scenario classified pointwise (asserted) and equal
     to the oracle; the same launch forced onto the stencil form too."""
     from finite_difference_amd import capi
-    base = _vanilla_solve(n, 60)
-    slots = 64 * w * npt
-    pad = (slots - n) // 2 if slots >= n else -1
-    lane_edges = [s - pad for s in (npt, npt + 1, 2 * npt - 2, 2 * npt - 1, 64 * npt - 1)]
-    pos = sorted({1, 2, n // 2, n - 3} | {i for i in lane_edges if 1 <= i <= n - 3})
-    solves = [_with_exceptional_rows(base, i) for i in pos] + [base]
+    pos, solves = exceptional_positions(w, npt, n)
     from finite_difference_amd.engine import pack_vc
     g = pack_vc(solves, list(range(len(solves))))
     assert np.all(capi.vc_forms(g.n_nodes, g.n_time, g.n_ranna, g.diag) == 1)
@@ -288,21 +244,7 @@ def test_mixed_forms_in_one_launch():
     import dataclasses
     from finite_difference_amd import capi
     from finite_difference_amd.engine import pack_vc
-    n, m = 1025, 120
-    weekly = [(V0 + dt.timedelta(days=7 * i)).isoformat() for i in range(1, 27)]
-    ko = make(dict(spot=100.0, strike=100.0, volatility=0.25, option_type="call",
-                   barrier_type="up-and-out", upper_barrier=125.0, monitoring_dates=weekly,
-                   flat_rate_nacc=0.05, num_space_nodes=n - 1, num_time_steps=m), None,
-              explicit_sign="corrected")._grid_solves()[2][0]
-    van = _vanilla_solve(n, m, "call")
-    refsign = make(dict(spot=100.0, strike=100.0, volatility=0.25, option_type="put",
-                        barrier_type="none", flat_rate_nacc=0.05, num_space_nodes=n - 1,
-                        num_time_steps=m), None)._grid_solves()[2][0]
-    D = van.diag.copy()
-    for i in (100, 400, 800):
-        D[1, 3, i] *= 1.001
-    odd = dataclasses.replace(van, diag=D)
-    solves = [ko, van, refsign, odd]
+    solves = mixed_forms()
     g = pack_vc(solves, list(range(4)))
     assert capi.vc_forms(g.n_nodes, g.n_time, g.n_ranna, g.diag).tolist() == [1, 1, 1, 0]
     got = Engine().run_vc(solves)
@@ -352,27 +294,6 @@ def test_vc_forms_classify_the_reference_rows_pointwise():
         capi.vc_force_variant(0, 0, False)
 
 
-def _random_rows(sv, seed, alpha, spread):
-    """A copy of `sv` whose implicit rows are random and, in many rows, NOT
-    diagonally dominant: main_i in [1, 2], sub_i / main_i and sup_i / main_i
-    drawn from [-spread, spread] (|sub| + |sup| up to 2 spread |main|); the
-    explicit rows alpha times the implicit off-diagonals plus a random
-    diagonal (the pointwise form's shape).  Both phases."""
-    import dataclasses
-    rng = np.random.default_rng(seed)
-    D = sv.diag.copy()
-    n = sv.n_nodes
-    for ph in range(2):
-        m = 1.0 + rng.random(n)
-        sub = m * rng.uniform(-spread, spread, n)
-        sup = m * rng.uniform(-spread, spread, n)
-        inner = slice(1, n - 1)  # rows 0 and n-1 stay Dirichlet rows
-        D[ph, 0, inner], D[ph, 1, inner], D[ph, 2, inner] = sub[inner], m[inner], sup[inner]
-        D[ph, 3, inner], D[ph, 5, inner] = alpha * sub[inner], alpha * sup[inner]
-        D[ph, 4, inner] = alpha * m[inner] + rng.uniform(-0.2, 0.2, n)[inner]
-    return dataclasses.replace(sv, diag=D)
-
-
 def _serial_pivots(diag_phase):
     """The reference's serial sweep (_solve_tridiagonal,
     discrete_barrier_fdm_pricer_2.py:282-290): pivots beta_i and the
@@ -404,8 +325,7 @@ def test_factor_scan_matches_serial_sweep_on_non_dominant_rows(alpha, spread):
     oracle, in the pointwise form and forced onto the stencil form."""
     from finite_difference_amd import capi
     from finite_difference_amd.engine import pack_vc
-    base = _vanilla_solve(1025, 24)
-    solves = [_random_rows(base, seed, alpha, spread) for seed in range(6)]
+    solves = factor_scan(alpha, spread)
     contraction = []
     for sv in solves:
         for ph in range(2):
@@ -442,18 +362,7 @@ def test_exceptional_rows_split_over_both_phases(w, npt, n):
     import dataclasses
     from finite_difference_amd import capi
     from finite_difference_amd.engine import pack_vc
-    base = _vanilla_solve(n, 60)
-    solves = []
-    for i1 in (1, npt - 1, npt, n // 2, n - 4):
-        D = base.diag.copy()
-        D[0, 3, i1 + 1] *= 1.001  # Rannacher phase: row i1 + 1
-        D[0, 5, i1 + 1] *= 0.999
-        D[1, 3, i1] *= 1.001      # Crank-Nicolson phase: row i1
-        D[1, 5, i1] *= 0.999
-        solves.append(dataclasses.replace(
-            base, diag=D, ko_lo=n // 4, ko_hi=3 * n // 4,
-            mon_steps=list(range(5, base.n_time + 1, 5)),
-            mon_rebates=[0.5] * len(range(5, base.n_time + 1, 5))))
+    solves = split_phase_rows(w, npt, n)
     g = pack_vc(solves, list(range(len(solves))))
     assert np.all(capi.vc_forms(g.n_nodes, g.n_time, g.n_ranna, g.diag) == 1)
     ref = oracle_engine().run_vc(solves)
