@@ -582,19 +582,23 @@ constexpr int kScanLdsDoubles = 4 * 2 * 64;
 // kStampScen scenarios and kStampSteps steps from kStampStep0, written by lane
 // 0 into the scenario's Rannacher save slice (vsave, read only in steps m <
 // n_ranna) at [step - kStampStep0][16]; slot 15 of the first step row holds
-// the wave's HW_ID and slot 14 its XCC_ID.  The product build compiles no
-// stamp.
+// the wave's HW_ID and slot 14 its XCC_ID.  The one-wave two-pass IT march
+// (config 2) has no save slice: its stamps, same scenarios, steps and row
+// layout, go to a buffer of their own (it_stamp_buf, read back through
+// fdcn_diag_it_stamps).  The product build compiles no stamp.
 #ifdef FDCN_STAMPS
 constexpr int kStampScen = 64, kStampStep0 = 1024, kStampSteps = 32;
+__device__ double it_stamp_buf[kStampScen * kStampSteps * 16];
 #define FDCN_STAMP(k)                                                                 \
   do {                                                                                \
-    if constexpr (kRec) {                                                             \
+    if constexpr (kRec || (IT && kTP)) {                                              \
       if (scen < kStampScen && stamp_m >= kStampStep0 &&                              \
           stamp_m < kStampStep0 + kStampSteps) {                                      \
         const unsigned long long tt_ = __builtin_amdgcn_s_memtime();                  \
+        double* row_ = kRec ? A.vsave + (size_t)scen * 64 * NPT                       \
+                            : it_stamp_buf + (size_t)scen * kStampSteps * 16;         \
         if (lane == 0)                                                                \
-          A.vsave[(size_t)scen * 64 * NPT + (stamp_m - kStampStep0) * 16 + (k)] =     \
-              __longlong_as_double((long long)tt_);                                   \
+          row_[(stamp_m - kStampStep0) * 16 + (k)] = __longlong_as_double((long long)tt_); \
       }                                                                               \
     }                                                                                 \
   } while (0)
@@ -642,8 +646,18 @@ __host__ __device__ inline int lds_doubles_per_scen(int lz) {
 // config 3 6.66 -> 6.46 ms, config 5 unchanged; pass 1 + scan (this) a
 // further -1.3 / -2.2 % on config 2 (two boxes), -0.6 % on config 5, config
 // 3 neutral; raising it over the Sherman-Morrison broadcast lost time.
+// The IT two-pass step raises forward pass 1 and the backward scan only: its
+// forward carry section is issued inside backward pass 1 (solve_tp).
 #define FDCN_PRIO_HI() __builtin_amdgcn_s_setprio(3)
 #define FDCN_PRIO_LO() __builtin_amdgcn_s_setprio(0)
+// Diagnostic builds only (-DFDCN_IT_SPLIT_CARRY): the IT two-pass step with
+// its forward carry section in front of backward pass 1 instead of inside it
+// (see solve_tp) -- the "before" of the stamp timelines and A/B runs.
+#ifdef FDCN_IT_SPLIT_CARRY
+constexpr bool kItCarryInPass = false;
+#else
+constexpr bool kItCarryInPass = true;
+#endif
 // Occupancy target: the config-3 throughput variant (CN, one wave, 16-node
 // chunks) is held to 128 VGPRs, 4 waves per SIMD instead of 3 (measured
 // 5.56 -> 5.44 ms per launch with the scan weights of stages 2-5 in LDS,
@@ -1600,7 +1614,85 @@ fdcn_march(KArgs A) {
       }
       a[j] = w;
     }
+    FDCN_STAMP(1);
     double e = a[0];
+    if constexpr (IT && kItCarryInPass) {
+      // IT: the forward carry section -- sub-chain joins, scan stages 0-1,
+      // the carry from the lane below and the CC[j] -- is a dependent chain
+      // of S + 4 and 2 S instructions around the rare stages 2-5, with two
+      // wait states in front of every DPP move.  Backward pass 1 reads none
+      // of it (only the zero-carry values and bm; CC[j] enters after the
+      // last link), so the section is issued inside it, one instruction
+      // after every kLps links (sub-chains round-robin): the links cover its
+      // latencies and the DPP wait states.  Plain FMAs between full
+      // scheduling barriers: the same instructions on the same operands, in
+      // another order (inline asm here would draw an s_nop per dependent
+      // pair).  The whole region runs at the base priority, like the backward
+      // pass it sits in.  Config 2, five alternating runs against the split
+      // layout: 9.86 -> 9.52 ms on one box and 9.85 -> 9.70 on another; at
+      // priority 3 throughout 10.01, at 1 or 2 9.94-10.0; three links per
+      // instruction instead of two 9.75 against 9.70.
+      constexpr int kLinks = S * (M - 1), kA = S + 4, kB = 2 * S, kLps = 2;
+      double y[S], ab[S];
+#pragma unroll
+      for (int j = 0; j < S; ++j) y[j] = Wr(j * M + M - 1);
+      auto link = [&](int l) __attribute__((always_inline)) {
+        const int j = l % S, k = j * M + M - 2 - l / S;
+        // a short lane's last real node starts its sub-chain with a zero
+        // carry (bw1l = 0)
+        y[j] = fma(k == NPT - 2 ? bw1l : bm, y[j], Wr(k));
+        Wr(k) = y[j];
+      };
+      auto links2 = [&](int t) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < kLps; ++u)
+          if (kLps * t + u < kLinks) link(kLps * t + u);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      double b = 0.0, sh = 0.0, cin = 0.0, c = 0.0;
+      FDCN_PRIO_LO();
+#pragma unroll
+      for (int n = 0; n < kA; ++n) {
+        links2(n);
+        if (n < S - 1) e = fma(n + 1 == S - 1 ? mulLF : fmM, e, a[n + 1]);
+        else if (n == S - 1) sh = shfl_up1(b = e, 1);
+        else if (n == S) b = fma(FW[0], sh, b);
+        else if (n == S + 1) sh = dpp_move<kDppWaveShr1>(b);
+        else if (n == S + 2) sh = dpp_move<kDppWaveShr1>(sh);
+        else b = fma(FW[1], sh, b);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // (a use in this block: the links above stay in front of the branch,
+      // where nothing past it would hold them)
+#pragma unroll
+      for (int j = 0; j < S; ++j) asm volatile("" : : "v"(y[j]));
+      if (nst_f > 2) {
+#pragma unroll
+        for (int j = 2; j < 6; ++j)
+          if (j < nst_f) b = fma(FW[j], scan_up(b, 1 << j, lane4), b);
+      }
+#pragma unroll
+      for (int n = 0; n < kB; ++n) {
+        links2(kA + n);
+        // into sub-chain 0 from the lane below (0 on lane 0 and dropped on
+        // inactive lanes by fm_act), then across the sub-chains
+        if (n == 0) cin = shfl_up1(b, 1);
+        else if (n == 1) CC[0] = fm_act * (c = cin);
+        else if (n % 2 == 0) c = fma(n == 2 ? fmM_act : fmM, c, a[n / 2 - 1]);
+        else CC[n / 2] = fm * c;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      FDCN_STAMP(2);
+#pragma unroll
+      for (int l = kLps * (kA + kB); l < kLinks; ++l) link(l);
+      // the sub-chains' start values with their forward carries, zero
+      // backward carry
+#pragma unroll
+      for (int j = 0; j < S; ++j) ab[j] = fma(CC[j], j == S - 1 ? p0l : P0u, y[j]);
+#pragma unroll
+      for (int j = 0; j < S; ++j) a[j] = ab[j];
+      FDCN_STAMP(3);
+    } else {
 #pragma unroll
     for (int j = 1; j < S; ++j) e = fma(j == S - 1 ? mulLF : fmM, e, a[j]);
     // stage 0 unconditional on the split form: the config-3 grids all need
@@ -1627,6 +1719,7 @@ fdcn_march(KArgs A) {
       c = fma(j == 1 ? fmM_act : fmM, c, a[j - 1]);
       CC[j] = fm * c;
     }
+    FDCN_STAMP(2);
     // backward pass 1 in place; a short lane's last real node starts its
     // sub-chain with a zero carry (bw1l = 0)
     FDCN_PRIO_LO();
@@ -1644,6 +1737,8 @@ fdcn_march(KArgs A) {
       // the sub-chain's start value with its forward carry, zero backward carry
       a[j] = fma(CC[j], j == S - 1 ? p0l : P0u, y);
     }
+    FDCN_STAMP(3);
+    }  // the split layout
     FDCN_PRIO_HI();
     e = a[S - 1];
 #pragma unroll
@@ -1663,6 +1758,7 @@ fdcn_march(KArgs A) {
     DD[S - 1] = shfl_dn1(cb, 1);  // lane 63 receives 0
 #pragma unroll
     for (int j = S - 2; j >= 0; --j) DD[j] = fma(j + 1 == S - 1 ? mulLB : bmM, DD[j + 1], a[j + 1]);
+    FDCN_STAMP(4);
   };
   (void)solve_tp;
 
@@ -2079,13 +2175,15 @@ fdcn_march(KArgs A) {
   for (int m = m0; m < m_end; ++m) {
 #ifdef FDCN_STAMPS
     stamp_m = m;
-    if constexpr (kRec) {
+    if constexpr (kRec || (IT && kTP)) {
       if (scen < kStampScen && m == kStampStep0 && lane == 0) {
         unsigned hw, xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        A.vsave[(size_t)scen * 64 * NPT + 15] = (double)hw;
-        A.vsave[(size_t)scen * 64 * NPT + 14] = (double)xcc;
+        double* row = kRec ? A.vsave + (size_t)scen * 64 * NPT
+                           : it_stamp_buf + (size_t)scen * kStampSteps * 16;
+        row[15] = (double)hw;
+        row[14] = (double)xcc;
       }
     }
 #endif
@@ -2311,7 +2409,9 @@ fdcn_march(KArgs A) {
       // sched_barriers hold the loads where they are written.  Two groups
       // ahead measured 0.4 % slower at the same register count (DESIGN
       // section 3); with two sub-chains at 247 registers it gained 0.13 ms,
-      // under three spreads (10.06 against 10.19 ms).
+      // under three spreads (10.06 against 10.19 ms); with
+      // the forward carries inside backward pass 1 it gains nothing (9.52
+      // against 9.52 ms; alone 9.72 against 9.86, 1.3 spreads).
       constexpr int kGroups = NPT / 4;
       constexpr int kPkAhead = kGroups < 1 ? kGroups : 1;
       double pk[kGroups > 0 ? kGroups : 1][4];
@@ -2385,6 +2485,7 @@ fdcn_march(KArgs A) {
               "s"(ph.inv_r), "s"(cq));
       }
       }  // NPT % 4 == 0
+      FDCN_STAMP(5);
 #undef FDCN_TP_K
     } else {
     // ---- 2. tridiagonal solve ---------------------------------------------
@@ -3273,5 +3374,16 @@ int fdcn_forced_variant(int32_t* waves, int32_t* npt, int32_t* flavour) {
   return FDCN_OK;
 }
 
+#ifdef FDCN_STAMPS
+// Diagnostic builds only (tools/stamp_timeline.py --it): the IT march's stamp
+// buffer, [kStampScen][kStampSteps][16] doubles, of the launches so far.
+int fdcn_diag_it_stamps(double* out, int32_t n_doubles) {
+  if (!out || n_doubles != kStampScen * kStampSteps * 16) return FDCN_EINVAL;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(it_stamp_buf), sizeof(double) * n_doubles) ==
+                 hipSuccess
+             ? FDCN_OK
+             : FDCN_EHIP;
+}
+#endif
 
 }  // extern "C"
