@@ -13,3 +13,4 @@ from .mc_barrier import (NacaCurve, BarrierSpec, RebateSpec, MCConfig,  # noqa: 
                          price_discrete_barrier_mc, mc_barrier_batch, merge_mc_stats)
 from .bgk_barrier import DiscreteBarrierBGKPricer, bgk_price_batch  # noqa: F401
 from .american_barrier import AmericanBarrierFDMPricer  # noqa: F401
+from .american_knockin import AmericanKnockInFDMPricer  # noqa: F401

@@ -23,9 +23,10 @@ six numbers per trade come back.  With another engine (the CPU oracle in the
 tests) the host-side jump and epilogue below are used.
 
 What happens between two segments is an ordered list of events per grid job
-(``_job_events``): the dividend jump here, and the knock-out of a monitoring
-date in american_barrier.py's subclass; vanilla and barrier trades march
-together in ``greeks_many`` / ``prefetch_many``.
+(``_job_events``): the dividend jump here, the knock-out of a monitoring
+date in american_barrier.py's subclass, and the knock-in of american_knockin.py,
+whose jobs march two coupled chains; vanilla and barrier trades march together
+in ``greeks_many`` / ``prefetch_many``.
 """
 from __future__ import annotations
 
@@ -411,7 +412,8 @@ class AmericanFDMPricer:
         """(events, pts, steps, restart) of one grid job on the current grid:
         events[i] is the ordered list of maps applied to the value vector
         between segment i and segment i + 1 -- ("div", cash) for a dividend
-        jump, ("ko", ko_lo, ko_hi, rebate) for a knock-out (subclasses) --
+        jump, ("ko", ko_lo, ko_hi, rebate) for a knock-out, ("ki", ko_lo,
+        ko_hi) for a knock-in from the coupled chain (subclasses) --
         and restart[i] says whether segment i restarts the Rannacher steps
         (the reference: the first segment, and every segment of a call,
         fd_american_equity.py:825-843)."""
@@ -447,6 +449,24 @@ class AmericanFDMPricer:
         if event[0] == "div":
             return self._apply_dividend_jump(v, event[1])
         return self._apply_knockout(v, event[1], event[2], event[3])
+
+    # A job marches one chain here: the vector job["v"] (device: the slot
+    # job["slot"]).  american_knockin.py's jobs march a second, coupled chain
+    # job["w"] / job["wslot"]; the three hooks below are what the march loops
+    # ask a job's owner, called with the job's grid restored.
+    def _job_solves(self, job: dict, seg: int) -> list:
+        """(chain key, Solve) of every chain of `job` that marches segment seg."""
+        return [("v", self._segment_solve(job["v"], job["pts"][seg], job["pts"][seg + 1],
+                                          job["steps"][seg], job["restart"][seg]))]
+
+    def _apply_job_event(self, job: dict, seg: int, event: tuple) -> None:
+        """One event after segment seg on the job's host vectors."""
+        job["v"] = self._apply_event(job["v"], event)
+
+    def _jump_chains(self, job: dict, seg: int) -> list:
+        """(chain key, strike_call) of every chain a dividend jump after
+        segment seg maps on the device; strike_call < 0: no exercise floor."""
+        return [("v", self._strike_snapped_for(job) if self.option_type == "call" else -1.0)]
 
     def _skip_solve(self) -> bool:
         """True when price and Greeks are known without a solve."""
@@ -494,10 +514,11 @@ class AmericanFDMPricer:
     @staticmethod
     def _march_jobs(jobs: list, engine: Engine) -> None:
         """March grid jobs of any number of trades in segment lock-step: every
-        job's segment i goes into one engine.run (one launch per distinct
-        (n_nodes, n_time)), then each job's events at that time (dividend
-        jump, knock-out), then segment i+1; finally each job's value vector
-        is cached on its owner."""
+        job's segment i (both chains of a knock-in job) goes into one
+        engine.run (one launch per distinct (mode, n_nodes, n_time)), then
+        each job's events at that time (dividend jump, knock-out, knock-in),
+        then segment i+1; finally each job's value vector is cached on its
+        owner."""
         if not jobs:
             return
         n_seg = max(len(j["steps"]) for j in jobs)
@@ -513,15 +534,15 @@ class AmericanFDMPricer:
                     p._restore(j["grid"])
                     if len(p.s_nodes) - 1 < 2:
                         raise RuntimeError("Spatial grid too coarse.")
-                    solves.append(p._segment_solve(j["v"], j["pts"][seg], j["pts"][seg + 1],
-                                                   j["steps"][seg], j["restart"][seg]))
+                    for chain, s in p._job_solves(j, seg):
+                        solves.append(s)
+                        owners.append((j, chain))
                 finally:
                     p.sigma = sigma0
                     p._restore(saved)
-                owners.append(j)
             if solves:
-                for j, v in zip(owners, engine.run(solves)):
-                    j["v"] = v
+                for (j, chain), v in zip(owners, engine.run(solves)):
+                    j[chain] = v
             for j in jobs:
                 if seg < len(j["events"]):
                     p = j["owner"]
@@ -530,7 +551,7 @@ class AmericanFDMPricer:
                         p.sigma = j["sigma"]
                         p._restore(j["grid"])
                         for event in j["events"][seg]:
-                            j["v"] = p._apply_event(j["v"], event)
+                            p._apply_job_event(j, seg, event)
                     finally:
                         p.sigma = sigma0
                         p._restore(saved)
@@ -590,14 +611,17 @@ class AmericanFDMPricer:
         """_march_jobs with the value vectors in HBM: segment i of every job in
         lock-step launches (initial vectors: the payoff, then the previous
         segment's slots), the events between segments on the device (the
-        spline jumps into new slots, the knock-outs in place).  A job of more
-        than one segment uploads its payoff once: its marches and knock-outs
-        name that slot.  Leaves each job's final slot in job["slot"]."""
+        spline jumps into new slots, the knock-outs and knock-ins in place).
+        A job of more than one segment uploads its payoff once: its IT marches
+        and knock-outs name that slot.  Leaves each job's final slot in
+        job["slot"] (a knock-in job's coupled chain: job["wslot"])."""
         n_seg = max(len(j["steps"]) for j in jobs)
+        slot_of = {"v": "slot", "w": "wslot"}  # chain key -> where its slot is kept
         by_n: Dict[int, list] = {}
         for j in jobs:
             j["pay"] = None
-            if len(j["steps"]) > 1:
+            # a knock-in job whose coupled IT chain never marches has no use for it
+            if len(j["steps"]) > 1 and j.get("w_last", 0) >= 0:
                 by_n.setdefault(len(j["grid"]["s_nodes"]), []).append(j)
         for js in by_n.values():
             pay = []
@@ -625,26 +649,24 @@ class AmericanFDMPricer:
                     p._restore(j["grid"])
                     if len(p.s_nodes) - 1 < 2:
                         raise RuntimeError("Spatial grid too coarse.")
-                    solves.append(p._segment_solve(j["v"], j["pts"][seg], j["pts"][seg + 1],
-                                                   j["steps"][seg], j["restart"][seg]))
+                    for chain, s in p._job_solves(j, seg):
+                        solves.append(s)
+                        owners.append((j, chain))
                 finally:
                     p.sigma = sigma0
                     p._restore(saved)
-                owners.append(j)
             if solves:
-                ps = [j["pay"] for j in owners]
+                ps = [j["pay"] if s.it else None for (j, _), s in zip(owners, solves)]
                 if seg > 0:
-                    vs = [j["slot"] for j in owners]
-                elif all(j["pay"] is not None and j["v_is_payoff"] for j in owners):
-                    vs = ps  # every chain starts from the payoff it has uploaded
-                else:
-                    vs = None
+                    vs = [j[slot_of[c]] for j, c in owners]
+                else:  # a chain that starts from the payoff it has uploaded names the slot
+                    vs = [j["pay"] if c == "w" or j["v_is_payoff"] else None for j, c in owners]
                 if all(x is None for x in ps):
                     slots = engine.march_slots(sess, solves, vs)
                 else:
                     slots = engine.march_slots(sess, solves, vs, ps)
-                for j, sl in zip(owners, slots):
-                    j["slot"] = int(sl)
+                for (j, c), sl in zip(owners, slots):
+                    j[slot_of[c]] = int(sl)
             # the k-th event of every job at this time, one launch per kind and
             # grid size (a job's own events keep their order)
             here = [j for j in jobs if seg < len(j["events"])]
@@ -661,13 +683,22 @@ class AmericanFDMPricer:
                                       [e[2] for e in ev], [e[3] for e in ev],
                                       [j["pay"] for j in js])
                         continue
-                    S = np.array([j["grid"]["s_nodes"] for j in js], dtype=np.float64)
-                    cash = [e[1] for e in ev]
-                    kc = [(j["owner"]._strike_snapped_for(j) if j["owner"].option_type == "call"
-                           else -1.0) for j in js]
-                    for j, sl in zip(js, sess.dividend_jump([j["slot"] for j in js], S, cash,
-                                                            kc)):
-                        j["slot"] = int(sl)
+                    if kind == "ki":  # U <- W on the knocked nodes; W's slot is only read
+                        sess.knockin([j["slot"] for j in js], n, [e[1] for e in ev],
+                                     [e[2] for e in ev], [j["wslot"] for j in js])
+                        continue
+                    # A knock-in job's jump maps both of its chains, so its
+                    # coupled chain can only jump in the round of this event:
+                    # after the round of the knock-in that reads it, which
+                    # stands before the jump in the job's list (and the jump
+                    # writes new slots, it never changes the one that was read).
+                    ent = [(j, c, kc, e[1]) for j, e in zip(js, ev)
+                           for c, kc in j["owner"]._jump_chains(j, seg)]
+                    S = np.array([j["grid"]["s_nodes"] for j, *_ in ent], dtype=np.float64)
+                    out = sess.dividend_jump([j[slot_of[c]] for j, c, *_ in ent], S,
+                                             [x[3] for x in ent], [x[2] for x in ent])
+                    for (j, c, *_), sl in zip(ent, out):
+                        j[slot_of[c]] = int(sl)
 
     def _strike_snapped_for(self, job: dict) -> float:
         st = job["grid"]
@@ -822,15 +853,25 @@ class AmericanFDMPricer:
 
 
 def _job_slot_bytes(job: dict) -> int:
-    """Bytes of the slots one job's chain creates: one vector per march, one
-    per dividend jump (knock-outs run in place) and the uploaded payoff.  It
+    """Bytes of the slots one job's chains create: one vector per march, one
+    per dividend jump (knock-outs and knock-ins run in place) and the uploaded
+    payoff; both chains of a knock-in job count.  It
     counts slots, not device memory: the block of every march also holds its
     copy of the initial vectors, the kernel workspace and, where the payoff
     slots are not consecutive, the gathered payoff, all kept until the session
     ends -- several times this figure."""
     n_jump = sum(1 for evs in job["events"] for e in evs if e[0] == "div")
     n_seg = len(job["steps"])
-    return 8 * len(job["grid"]["s_nodes"]) * (n_seg + n_jump + (1 if n_seg > 1 else 0))
+    w_last = job.get("w_last")
+    if w_last is None:
+        return 8 * len(job["grid"]["s_nodes"]) * (n_seg + n_jump + (1 if n_seg > 1 else 0))
+    # a knock-in job: the coupled IT chain marches segments 0 .. w_last (the
+    # last one a knock-in reads) and jumps at the dividends before that
+    w = 0
+    if w_last >= 0:
+        w = w_last + 1 + 1 + sum(1 for evs in job["events"][:w_last] for e in evs
+                                 if e[0] == "div")
+    return 8 * len(job["grid"]["s_nodes"]) * (n_seg + n_jump + w)
 
 
 def greeks_many(pricers: Sequence[AmericanFDMPricer], dv_sigma: float = 0.01,
@@ -841,8 +882,8 @@ def greeks_many(pricers: Sequence[AmericanFDMPricer], dv_sigma: float = 0.01,
     lock-step, with the spline jumps and the knock-outs on the device) march
     in shared launches, and the readouts, Richardson extrapolations, vega and
     theta run on the device (FDCN_GK_AMERICAN); six numbers per trade come
-    back.  Results land in each pricer's cache.  Vanilla and barrier pricers
-    (american_barrier.py) mix freely.
+    back.  Results land in each pricer's cache.  Vanilla, knock-out and
+    knock-in pricers (american_barrier.py, american_knockin.py) mix freely.
 
     Every march creates slots, so the slots of a chain take about n_segments x
     n_nodes x 8 bytes per grid until its session ends: when that estimate for
@@ -910,8 +951,9 @@ def prefetch_many(pricers: Sequence[AmericanFDMPricer], dv_sigma: float = 0.01,
     dividends are one segment, so the whole set is one engine.run (one launch
     per distinct (n_nodes, n_time)); trades with dividends add one round per
     extra segment, shared by every trade, with the host's spline jumps in
-    between.  Knock-out dates of barrier trades (american_barrier.py) are
-    further segment boundaries, shared in the same way."""
+    between.  Monitoring dates of barrier trades (american_barrier.py,
+    american_knockin.py) are further segment boundaries, shared in the same
+    way."""
     pricers = [p for p in pricers if not p._skip_solve()]
     if not pricers:
         return

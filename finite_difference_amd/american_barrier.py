@@ -24,7 +24,8 @@ marching backward the knock-out comes first (monitoring sees the ex-dividend
 spot), then the dividend jump, with no steps in between.
 
 There is no in/out parity under early exercise, so the ``*-in`` types are not
-offered.  Without a barrier, or without a monitoring date in (valuation,
+priced here: AmericanKnockInFDMPricer (american_knockin.py) marches them as
+two coupled chains.  Without a barrier, or without a monitoring date in (valuation,
 maturity], every number equals AmericanFDMPricer's bit for bit.
 """
 from __future__ import annotations
@@ -69,7 +70,8 @@ class AmericanBarrierFDMPricer(AmericanFDMPricer):
         bt = str(barrier_type).lower()
         if bt.endswith("-in"):
             raise ValueError(f"barrier_type {barrier_type!r}: knock-in types have no in/out "
-                             "parity under early exercise and are not supported.")
+                             "parity under early exercise and are not supported here; "
+                             "use AmericanKnockInFDMPricer.")
         if bt != "none" and bt not in KO_TYPES:
             raise ValueError(f"Unsupported barrier_type: {barrier_type}")
         if bt in ("down-and-out", "double-out") and lower_barrier is None:

@@ -16,6 +16,8 @@
 //   fdcn_session_upload         host vectors into slots (a chain's payoff, once)
 //   fdcn_session_dividend_jump  spline remap of slots into new slots (device)
 //   fdcn_session_knockout       monitoring-date knock-out of slots, in place
+//   fdcn_session_knockin        monitoring-date knock-in: masked copy from other
+//                               slots (the coupled American chain), in place
 //   fdcn_session_greeks         per-trade readouts + combinations -> T x 6
 //                               scalars back to the host
 //   fdcn_session_fetch          whole vectors back (when a caller wants them)
@@ -126,6 +128,23 @@ knockout_kernel(int n, int chunks, const uint64_t* __restrict__ dst,
     x = (f >= x || f != f) ? f : x;
   }
   reinterpret_cast<double*>(dst[b])[j] = x;
+}
+
+// Knock-in event that couples two chains of an American knock-in march: on
+// the knocked nodes (j <= ko_lo or j >= ko_hi) of vector b, V_j <- src_j with
+// src the vector of another slot (the vanilla American value the holder owns
+// once the barrier is seen breached); every other node is left alone.  Same
+// shape as knockout_kernel: threads along the nodes, `chunks` workgroups of
+// 256 per vector, contiguous 8-byte loads and stores.  The value moves as 64
+// bits, so NaN payloads and signed zeros arrive as they are.
+__global__ void __launch_bounds__(256)
+knockin_kernel(int n, int chunks, const uint64_t* __restrict__ dst,
+               const uint64_t* __restrict__ src, const int32_t* __restrict__ ko_lo,
+               const int32_t* __restrict__ ko_hi) {
+  const int b = blockIdx.x / chunks;
+  const int j = (blockIdx.x % chunks) * 256 + threadIdx.x;
+  if (j >= n || (j > ko_lo[b] && j < ko_hi[b])) return;
+  reinterpret_cast<uint64_t*>(dst[b])[j] = reinterpret_cast<const uint64_t*>(src[b])[j];
 }
 
 // Dividend jump of one value vector per workgroup (fd_american_equity.py
@@ -760,6 +779,66 @@ int fdcn_session_knockout(fdcn_session* s, int32_t B, int32_t n_nodes, const int
                      floor_slots ? (const uint64_t*)(d + oF) : nullptr,
                      (const int32_t*)(d + oLo), (const int32_t*)(d + oHi),
                      (const double*)(d + oR));
+  S_TRY(hipGetLastError());
+  int32_t ev;
+  if ((rc = record(s, st, &ev))) return rc;
+  for (int32_t b = 0; b < B; ++b) s->slots.ev[(size_t)slots[b]] = ev;  // consumers wait for it
+  return FDCN_OK;
+}
+
+int fdcn_session_knockin(fdcn_session* s, int32_t B, int32_t n_nodes, const int32_t* slots,
+                         const int32_t* src_slots, const int32_t* ko_lo, const int32_t* ko_hi) {
+  if (B < 1 || n_nodes < 1) return sfail(FDCN_EINVAL, "knockin: B >= 1, n_nodes >= 1");
+  if (!slots || !src_slots || !ko_lo || !ko_hi)
+    return sfail(FDCN_EINVAL, "knockin: NULL argument (slots, src_slots, ko_lo, ko_hi)");
+  if (!s) return sfail(FDCN_EINVAL, "NULL session");
+  const int64_t chunks = ((int64_t)n_nodes + 255) / 256;
+  if (chunks * B > INT32_MAX) return sfail(FDCN_EINVAL, "knockin: batch too large for one launch");
+  int rc = check_slots(s, B, slots, n_nodes);
+  if (rc) return rc;
+  if ((rc = check_slots(s, B, src_slots, n_nodes))) return rc;
+  // as the knock-out: in place, so a slot named twice, or read as a source
+  // while another vector's event writes it, would depend on timing
+  std::vector<int32_t> sorted(slots, slots + B);
+  std::sort(sorted.begin(), sorted.end());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+    return sfail(FDCN_EINVAL, "knockin: a slot appears twice in slots");
+  for (int32_t b = 0; b < B; ++b)
+    if (std::binary_search(sorted.begin(), sorted.end(), src_slots[b]))
+      return sfail(FDCN_EINVAL, "knockin: source slot %d is one of slots", src_slots[b]);
+  Layout L;
+  const size_t oA = L.add(sizeof(uint64_t) * B);
+  const size_t oS = L.add(sizeof(uint64_t) * B);
+  const size_t oLo = L.add(sizeof(int32_t) * B);
+  const size_t oHi = L.add(sizeof(int32_t) * B);
+  char* h = s->pinned().get(L.size);
+  if (!h) return sfail(FDCN_ENOMEM, "hipHostMalloc(%zu) failed", L.size);
+  uint64_t* a = (uint64_t*)(h + oA);
+  uint64_t* f = (uint64_t*)(h + oS);
+  for (int32_t b = 0; b < B; ++b) {
+    a[b] = (uint64_t)s->slots.ptr[slots[b]];
+    f[b] = (uint64_t)s->slots.ptr[src_slots[b]];
+  }
+  memcpy(h + oLo, ko_lo, sizeof(int32_t) * B);
+  memcpy(h + oHi, ko_hi, sizeof(int32_t) * B);
+  hipStream_t st;
+  if ((rc = pick_stream(s, &st))) return rc;
+  // The ordering of fdcn_session_knockout: after everything the session has
+  // queued so far on every stream, which covers the marches that produced
+  // `slots` and the sources (often on another stream: the IT and the CN chain
+  // are different launch groups) and any earlier reader of `slots`.
+  for (hipStream_t other : s->streams) {
+    if (other == st) continue;
+    int32_t ev;
+    if ((rc = record(s, other, &ev))) return rc;
+    S_TRY(hipStreamWaitEvent(st, s->events[ev], 0));
+  }
+  char* d = nullptr;
+  if ((rc = alloc_block(s, st, L.size, &d))) return rc;
+  S_TRY(hipMemcpyAsync(d, h, L.size, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(knockin_kernel, dim3((unsigned)(chunks * B)), dim3(256), 0, st, n_nodes,
+                     (int)chunks, (const uint64_t*)(d + oA), (const uint64_t*)(d + oS),
+                     (const int32_t*)(d + oLo), (const int32_t*)(d + oHi));
   S_TRY(hipGetLastError());
   int32_t ev;
   if ((rc = record(s, st, &ev))) return rc;

@@ -306,15 +306,17 @@ class Engine:
                     payoff_slots: Optional[Sequence[Optional[int]]] = None) -> np.ndarray:
         """Launch `solves` in `sess` (one launch per shape, overlapping on the
         session's streams) and return the output slot of each solve.  With
-        v_init_slots, solve i starts from slot v_init_slots[i].  With
-        payoff_slots, IT solve i reads its exercise values from slot
+        v_init_slots, solve i starts from slot v_init_slots[i]; entries may be
+        None, and a launch group starts from slots when every solve in it has
+        one, else from the solves' own v_init.  With payoff_slots, IT solve i reads its exercise values from slot
         payoff_slots[i] (uploaded once for a chain of segments) instead of
         sending solve.payoff with the launch; a launch group takes that path
         when every solve in it has a slot."""
         out = np.empty(len(solves), dtype=np.int32)
         for g in group_solves(solves):
-            vs = None if v_init_slots is None else np.asarray(
-                [v_init_slots[i] for i in g.index], dtype=np.int32)
+            vs = None
+            if v_init_slots is not None and all(v_init_slots[i] is not None for i in g.index):
+                vs = np.asarray([v_init_slots[i] for i in g.index], dtype=np.int32)
             ps = None
             if payoff_slots is not None and g.it and all(
                     payoff_slots[i] is not None for i in g.index):

@@ -55,6 +55,8 @@ def _bind(L: ctypes.CDLL) -> None:
     L.fdcn_session_upload.argtypes = [_V, _I, _I, _V, _V]
     L.fdcn_session_knockout.restype = _I
     L.fdcn_session_knockout.argtypes = [_V, _I, _I, _V, _V, _V, _V, _V]
+    L.fdcn_session_knockin.restype = _I
+    L.fdcn_session_knockin.argtypes = [_V, _I, _I, _V, _V, _V, _V]
     L.fdcn_session_dividend_jump.restype = _I
     L.fdcn_session_dividend_jump.argtypes = [_V, _I, _I, _V, _V, _V, _V, _V]
     L.fdcn_session_greeks.restype = _I
@@ -279,6 +281,20 @@ class Session:
             raise ValueError("knockout: one threshold pair, rebate and floor slot per slot")
         capi._check(self._L.fdcn_session_knockout(self._h, B, int(n_nodes), _ptr(sl), _ptr(lo),
                                                   _ptr(hi), _ptr(R), _ptr(fs)))
+
+    def knockin(self, slots, n_nodes: int, ko_lo, ko_hi, src_slots) -> None:
+        """Knock-in event in place on `slots` (fdcn_session_knockin): nodes
+        j <= ko_lo[b] or j >= ko_hi[b] of vector b take the value of the same
+        node of the vector in src_slots[b]; the source slots are only read."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        B = sl.shape[0] if sl.ndim == 1 else -1
+        lo = np.ascontiguousarray(ko_lo, np.int32)
+        hi = np.ascontiguousarray(ko_hi, np.int32)
+        ss = np.ascontiguousarray(src_slots, np.int32)
+        if sl.ndim != 1 or lo.shape != (B,) or hi.shape != (B,) or ss.shape != (B,):
+            raise ValueError("knockin: one threshold pair and source slot per slot")
+        capi._check(self._L.fdcn_session_knockin(self._h, B, int(n_nodes), _ptr(sl), _ptr(ss),
+                                                 _ptr(lo), _ptr(hi)))
 
     def dividend_jump(self, slots, s_nodes: np.ndarray, cash, strike_call) -> np.ndarray:
         sl = np.ascontiguousarray(slots, np.int32)

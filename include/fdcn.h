@@ -47,7 +47,8 @@ extern "C" {
 
 /* 8: fdcn_session_upload, fdcn_session_knockout and fdcn_session_march_ps (the
  * American knock-out chain: monitoring events between IT segments) were added
- * after 7.
+ * after 7; fdcn_session_knockin (the American knock-in chain) joined later as
+ * an additive symbol, with the version left at 8.
  * 7: the BGK barrier pricer's Monte Carlo entry points (fdcn_mc_bgk_batch,
  * fdcn_mc_bgk_batch_dev, fdcn_mc_bgk_plan) were added after 6.
  * 6: the Monte Carlo discrete-barrier entry points (fdcn_mc_barrier_batch,
@@ -243,6 +244,23 @@ int fdcn_session_upload(fdcn_session* s, int32_t B, int32_t n_nodes, const doubl
 int fdcn_session_knockout(fdcn_session* s, int32_t B, int32_t n_nodes, const int32_t* slots,
                           const int32_t* ko_lo, const int32_t* ko_hi, const double* rebate,
                           const int32_t* floor_slots);
+
+/* Knock-in event of a discretely monitored American option, in place on
+ * `slots` [B] (no new slot):
+ *   V_j <- src_j   for j <= ko_lo[b] or j >= ko_hi[b]
+ * with src the vector in src_slots[b] (the vanilla American value the holder
+ * owns once the barrier is seen breached: the coupled chain of the knock-in
+ * march); all other nodes keep their value, and the source slots are only
+ * read.  Thresholds follow FDCN_I_KO_LO / FDCN_I_KO_HI (-1 / >= n_nodes: none
+ * on that side); ko_lo[b] >= ko_hi[b] copies every node.  Bit-identical to
+ * np.where(knocked, src, V), NaNs included.  Ordered as
+ * fdcn_session_knockout: after every call the session queued before it, and
+ * later consumers of `slots` wait for it.  B >= 1, n_nodes >= 1; a slot may
+ * appear once in `slots`, and no source slot may be one of `slots`.
+ * Additive: the symbol joined the exported surface without a change of
+ * FDCN_ABI_VERSION (still 8); a caller that needs it looks the symbol up. */
+int fdcn_session_knockin(fdcn_session* s, int32_t B, int32_t n_nodes, const int32_t* slots,
+                         const int32_t* src_slots, const int32_t* ko_lo, const int32_t* ko_hi);
 
 /* fdcn_session_march for an Ikonen-Toivanen march (it != 0 required) whose
  * payoff lies in earlier slots (payoff_slots [B], e.g. from

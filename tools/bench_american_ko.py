@@ -25,6 +25,14 @@ _job_events / _segment_solve per scenario); the first scenarios are checked
 against the facade's session path.  Prints one JSON line.  --dump-outputs DIR
 writes the chain's prices as DIR/american_ko_prices.npy.  Without a GPU it
 fails; there is no fallback.
+
+--knock-in times the American knock-in chain instead (american_knockin.py:
+the same trades as a down-and-in put, fdcn_session_knockin): per segment the
+Ikonen-Toivanen march of W (fdcn_session_march_ps, up to the last monitoring
+time), the Crank-Nicolson march of U and the knock-in event U <- W, 22 of
+them.  Same clock as `chain`; the line then holds ki_chain, the knock-out
+`chain` of the same process and the plain launch (chain_host is left out),
+and --dump-outputs writes american_ki_prices.npy.
 """
 from __future__ import annotations
 
@@ -51,10 +59,13 @@ def weekdays():
     return [d for d in days if d.weekday() < 5]
 
 
-def build_jobs(B: int, n_space: int, n_time: int, barrier: float, seed: int = 0):
+def build_jobs(B: int, n_space: int, n_time: int, barrier: float, seed: int = 0,
+               knock_in: bool = False):
     """One grid job per scenario: a single pricer re-pointed at each trade of
     the sweep (same dates and curve), as bench.py builds the vanilla batch."""
-    from finite_difference_amd import AmericanBarrierFDMPricer, market
+    from finite_difference_amd import (AmericanBarrierFDMPricer, AmericanKnockInFDMPricer,
+                                       market)
+    cls = AmericanKnockInFDMPricer if knock_in else AmericanBarrierFDMPricer
     curve = market.iso_curve(market.create_rate_df(math.exp(0.07053828272) - 1.0))
     p, jobs = None, []
     for i in range(B):
@@ -62,11 +73,12 @@ def build_jobs(B: int, n_space: int, n_time: int, barrier: float, seed: int = 0)
         strike = 140.0 + 70.0 * (j % 64) / 63.0
         sigma = 0.18 + 0.30 * ((j // 64) % 64) / 63.0
         if p is None:
-            p = AmericanBarrierFDMPricer(
+            p = cls(
                 spot=SPOT, strike=strike, valuation_date=VAL, maturity_date=MAT, sigma=sigma,
                 option_type="put", discount_curve=curve, forward_curve=curve,
                 num_space_nodes=n_space, num_time_steps=n_time, rannacher_steps=2,
-                barrier_type="down-and-out", lower_barrier=barrier, monitor_dates=weekdays())
+                barrier_type="down-and-in" if knock_in else "down-and-out",
+                lower_barrier=barrier, monitor_dates=weekdays())
         p._reset_trade(SPOT, strike, sigma)
         p._build_log_grid()
         jobs.append(p._make_job(p._state_key(sigma, n_time), sigma, n_time))
@@ -136,6 +148,67 @@ def run_chain(p, jobs, groups, payoff_slots: bool):
     return t_queued + t_wait, (t_queued, t_upload), out[:, 0].copy()
 
 
+def knockin_groups(p, jobs):
+    """The launch groups of the knock-in chain's two marches per segment: W
+    (Ikonen-Toivanen, segments 0 .. w_last) and U (Crank-Nicolson, all)."""
+    from finite_difference_amd import capi
+    from finite_difference_amd.engine import Group, pack
+    j0 = jobs[0]
+    same = ("pts", "steps", "restart", "w_restart", "w_last")
+    assert all(all(j[k] == j0[k] for k in same) for j in jobs)
+    W, U = [], []
+    for j in jobs:
+        p.sigma = j["sigma"]
+        p._restore(j["grid"])
+        for chain, s in p._job_solves(j, 0):
+            (W if chain == "w" else U).append(s)
+    first = [pack(W, list(range(len(W)))), pack(U, list(range(len(U))))]
+    del W, U
+
+    def variant(g0, seg, restart):
+        tau0, tau1, steps = j0["pts"][seg], j0["pts"][seg + 1], j0["steps"][seg]
+        P = g0.params.copy()
+        P[:, capi.P_DT] = (tau1 - tau0) / float(steps)
+        P[:, capi.P_TAU0] = tau0
+        return Group(g0.it, g0.n_nodes, int(steps), p.rannacher_steps if restart else 0, P,
+                     g0.iparams, g0.v_init, g0.payoff, g0.mon_step, g0.mon_rebate, g0.index)
+    gw = [variant(first[0], s, j0["w_restart"][s]) for s in range(j0["w_last"] + 1)]
+    gu = [variant(first[1], s, j0["restart"][s]) for s in range(len(j0["steps"]))]
+    assert np.array_equal(gw[0].params, first[0].params)
+    assert np.array_equal(gu[0].params, first[1].params)
+    return gw, gu
+
+
+def run_knockin_chain(p, jobs, gw, gu):
+    """run_chain for the knock-in: payoff uploaded once and named by W's
+    marches, U's first march sends its initial vectors, then everything stays
+    in slots; the prices are read from U."""
+    from finite_difference_amd.session import GK_READOUT, Session
+    n = gu[0].n_nodes
+    ev = [[j["events"][s][0] for j in jobs] for s in range(len(gu) - 1)]
+    assert all(e[0] == "ki" for es in ev for e in es)
+    lo = [np.array([e[1] for e in es], np.int32) for es in ev]
+    hi = [np.array([e[2] for e in es], np.int32) for es in ev]
+    with Session() as S:
+        t0 = time.perf_counter()
+        pay = S.upload(gw[0].payoff)
+        t_upload = time.perf_counter() - t0
+        w, u = pay, None
+        for s, g in enumerate(gu):
+            if s < len(gw):
+                w = S.march(gw[s], w, pay)
+            u = S.march(g, u)
+            if s < len(ev):
+                S.knockin(u, n, lo[s], hi[s], w)
+        t_queued = time.perf_counter() - t0
+        trades = [(GK_READOUT, [p._job_readout(j, int(sl), False)], ())
+                  for j, sl in zip(jobs, u)]
+        t1 = time.perf_counter()
+        out = S.greeks(trades)  # waits for the chain
+        t_wait = time.perf_counter() - t1
+    return t_queued + t_wait, (t_queued, t_upload), out[:, 0].copy()
+
+
 def run_plain(g, launches: int, warmup: int):
     import torch
     from finite_difference_amd import capi
@@ -190,6 +263,9 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--dump-outputs", default="", metavar="DIR")
+    ap.add_argument("--knock-in", action="store_true",
+                    help="time the knock-in chain (down-and-in at --barrier) beside the "
+                         "knock-out chain and the plain launch")
     args = ap.parse_args()
 
     from finite_difference_amd import capi
@@ -199,6 +275,8 @@ def main() -> int:
     groups, plain = segment_groups(p, jobs, args.n_time)
     t_plan = time.perf_counter() - t0
 
+    if args.knock_in:
+        return main_knock_in(args, p, jobs, groups, plain, t_plan)
     res = {}
     for name, ps in (("chain", True), ("chain_host", False)):
         runs = [run_chain(p, jobs, groups, ps) for _ in range(args.warmup + args.reps)]
@@ -240,6 +318,51 @@ def main() -> int:
         os.makedirs(args.dump_outputs, exist_ok=True)
         np.save(os.path.join(args.dump_outputs, "american_ko_prices.npy"), prices)
         line["dumped"] = {"american_ko_prices": list(prices.shape)}
+    print(json.dumps(line))
+    return 0 if line["parity"]["ok"] and line["all_finite"] else 3
+
+
+def main_knock_in(args, p, jobs, groups, plain, t_plan: float) -> int:
+    t0 = time.perf_counter()
+    q, ki_jobs = build_jobs(args.batch, args.n_space, args.n_time, args.barrier, knock_in=True)
+    gw, gu = knockin_groups(q, ki_jobs)
+    t_plan += time.perf_counter() - t0
+
+    def spread(runs):
+        sec = [r[0] for r in runs]
+        return {"median": statistics.median(sec) * 1e3, "min": min(sec) * 1e3,
+                "max": max(sec) * 1e3,
+                "host_calls_ms": statistics.median([r[1][0] for r in runs]) * 1e3}
+    ki = [run_knockin_chain(q, ki_jobs, gw, gu) for _ in range(args.warmup + args.reps)]
+    ki = ki[args.warmup:]
+    ko = [run_chain(p, jobs, groups, True) for _ in range(args.warmup + args.reps)]
+    ko = ko[args.warmup:]
+    plain_t, device = run_plain(plain, args.reps, args.warmup)
+    plain_med = statistics.median(plain_t)
+    prices = ki[-1][2]
+    line = {
+        "metric": "american_ki_chain_ms",
+        "value": spread(ki)["median"],
+        "device": device,
+        "batch": args.batch, "n_space": args.n_space, "n_time": args.n_time,
+        "segments": len(gu), "w_segments": len(gw),
+        "segment_steps": [int(g.n_time) for g in gu],
+        "barrier": args.barrier, "reps": args.reps, "warmup": args.warmup,
+        "ki_chain_ms": spread(ki),
+        "chain_ms": spread(ko),
+        "plain_it_batch_dev_ms": {"median": plain_med * 1e3, "min": min(plain_t) * 1e3,
+                                  "max": max(plain_t) * 1e3},
+        "ki_over_chain": spread(ki)["median"] / spread(ko)["median"],
+        "ki_over_plain": spread(ki)["median"] * 1e-3 / plain_med,
+        "plan_seconds": t_plan,
+        "parity": facade_parity(q, ki_jobs, prices),
+        "all_finite": bool(np.all(np.isfinite(prices))),
+        "price_range": [float(prices.min()), float(prices.max())],
+    }
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "american_ki_prices.npy"), prices)
+        line["dumped"] = {"american_ki_prices": list(prices.shape)}
     print(json.dumps(line))
     return 0 if line["parity"]["ok"] and line["all_finite"] else 3
 
