@@ -31,7 +31,8 @@ HOST_SRCS := $(CSRC)/fdcn_host.hip $(CSRC)/fdcn_plan.hip
 HDRS := include/fdcn.h include/fdcn_diag.h $(CSRC)/fdcn_shared.h $(CSRC)/fdcn_session_book.h \
         $(CSRC)/fdcn_philox.h
 DEV_OBJS := build/obj/fdcn_kernels.o build/obj/fdcn_analytic.o build/obj/fdcn_session.o \
-            build/obj/fdcn_vc.o build/obj/fdcn_mc.o build/obj/fdcn_mc_bgk.o
+            build/obj/fdcn_vc.o build/obj/fdcn_mc.o build/obj/fdcn_mc_bgk.o \
+            build/obj/fdcn_mc_lsm.o
 SAN_TESTS := tests/test_tau_sequence.py tests/test_capi_symbols.py tests/test_scenario_batch.py \
              tests/test_american_batch.py tests/test_barrier_host.py tests/test_american_host.py
 

@@ -46,7 +46,8 @@ EXPORTED = ("fdcn_cn_batch", "fdcn_it_batch", "fdcn_cn_batch_dev", "fdcn_it_batc
             "fdcn_vc_batch", "fdcn_vc_batch_dev", "fdcn_vc_plan", "fdcn_barrier_plan",
             "fdcn_vmath", "fdcn_american_plan", "fdcn_device_ordinals",
             "fdcn_mc_barrier_batch", "fdcn_mc_barrier_batch_dev", "fdcn_mc_plan",
-            "fdcn_mc_bgk_batch", "fdcn_mc_bgk_batch_dev", "fdcn_mc_bgk_plan")
+            "fdcn_mc_bgk_batch", "fdcn_mc_bgk_batch_dev", "fdcn_mc_bgk_plan",
+            "fdcn_mc_lsm_batch", "fdcn_mc_lsm_batch_dev", "fdcn_mc_lsm_plan")
 # include/fdcn_diag.h: test / tuning entry points, not the product boundary
 DIAG_EXPORTED = ("fdcn_force_variant", "fdcn_forced_variant", "fdcn_variant_name",
                  "fdcn_vc_force_variant", "fdcn_vc_variant_name", "fdcn_vc_forms",
@@ -67,6 +68,17 @@ BGK_MAX_G, BGK_NPARAM, BGK_NFLAG, BGK_NSTEP, BGK_NSTAT = 8, 7, 4, 4, 4
  BGK_P_REBATE) = range(7)
 BGK_F_PUT, BGK_F_SIDES, BGK_F_REBATE_MODE, BGK_F_STREAM = range(4)
 BGK_S_DRIFT, BGK_S_DIFF, BGK_S_MONITOR, BGK_S_DF_END = range(4)
+# least-squares Monte Carlo (enum fdcn_lsm_param / _flag / _step / _stat)
+LSM_MAX_STEPS, LSM_SUBRUN, LSM_MIN_FIT, LSM_NCOEF = 512, 4096, 64, 5
+LSM_NPARAM, LSM_NFLAG, LSM_NSTEP, LSM_NSTAT = 4, 3, 9, 8
+LSM_P_SPOT, LSM_P_STRIKE, LSM_P_LOWER, LSM_P_UPPER = range(4)
+LSM_F_PUT, LSM_F_KIND, LSM_F_STREAM = range(3)
+(LSM_S_DRIFT, LSM_S_DIFF, LSM_S_DF_STEP, LSM_S_DF_END, LSM_S_MONITOR, LSM_S_EXERCISE,
+ LSM_S_REBATE, LSM_S_CENTRE, LSM_S_ISCALE) = range(9)
+(LSM_O_PRICE, LSM_O_STDERR, LSM_O_FIT_VALUE, LSM_O_FIT_STDERR, LSM_O_SUM, LSM_O_SUM2,
+ LSM_O_INVALID, LSM_O_MIN_MARGIN) = range(8)
+LSM_KIND = {"none": 0, "down-and-out": 1, "up-and-out": 2, "double-out": 3, "down-and-in": 4,
+            "up-and-in": 5, "double-in": 6}
 
 
 class FdcnError(RuntimeError):
@@ -268,6 +280,16 @@ def lib() -> ctypes.CDLL:
                                                 ctypes.c_uint64, _I64, _V, _V, _V, _I64, _V]
             L.fdcn_mc_bgk_plan.restype = _I
             L.fdcn_mc_bgk_plan.argtypes = [_I64, _I, _PI, _PI, ctypes.POINTER(ctypes.c_int64)]
+            L.fdcn_mc_lsm_batch.restype = _I
+            L.fdcn_mc_lsm_batch.argtypes = [_I, _I, _I, _I, _V, _V, _V, ctypes.c_uint64, _I64, _V,
+                                            _V, _V]
+            L.fdcn_mc_lsm_batch_dev.restype = _I
+            L.fdcn_mc_lsm_batch_dev.argtypes = [_I, _I, _I, _I, _V, _V, _V, ctypes.c_uint64, _I64,
+                                                _V, _V, _V, _V, _I64, _V]
+            L.fdcn_mc_lsm_plan.restype = _I
+            L.fdcn_mc_lsm_plan.argtypes = [_I, _I, _I, _PI, ctypes.POINTER(ctypes.c_int64),
+                                           ctypes.POINTER(ctypes.c_int64),
+                                           ctypes.POINTER(ctypes.c_int64)]
             L.fdcn_mc_normals.restype = _I
             L.fdcn_mc_normals.argtypes = [_I64, _I, ctypes.c_uint64, _I, _I64, _V]
             _lib = L
@@ -759,3 +781,51 @@ def mc_bgk_batch_dev(B: int, G: int, n_steps: int, n_obs: int, antithetic: bool,
         int(B), int(G), int(n_steps), int(n_obs), 1 if antithetic else 0, params_ptr, flags_ptr,
         step_ptr, z_ptr, int(seed) & (2 ** 64 - 1), int(obs_first), stats_ptr, payoff_ptr,
         workspace_ptr, int(workspace_bytes), stream_ptr))
+
+
+def mc_lsm_plan(n_steps: int, G: int, antithetic: bool) -> dict:
+    """Geometry of a least-squares Monte Carlo launch (fdcn_mc_lsm_plan; host
+    only): observations per sub-run, workspace bytes per contract, doubles per
+    contract of the value dump and of the coefficient dump."""
+    per = ctypes.c_int32()
+    ws, nv, nc = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    _check(lib().fdcn_mc_lsm_plan(int(n_steps), int(G), 1 if antithetic else 0, ctypes.byref(per),
+                                  ctypes.byref(ws), ctypes.byref(nv), ctypes.byref(nc)))
+    return dict(obs_per_subrun=per.value, ws_bytes_per_contract=ws.value,
+                values_per_contract=nv.value, coef_per_contract=nc.value)
+
+
+def mc_lsm_batch(params, flags, step, G: int, antithetic: bool, *, seed: int = 0,
+                 obs_first: int = 0, want_values: bool = False, want_coef: bool = False):
+    """fdcn_mc_lsm_batch on host arrays -> (stats [B, LSM_NSTAT], values
+    [B, G * LSM_SUBRUN] or None, coef [B, G, n_steps, LSM_NCOEF] or None).
+    params [B, LSM_NPARAM], flags [B, LSM_NFLAG], step [B, n_steps, LSM_NSTEP]."""
+    require_device()
+    P = _f64(params).reshape(-1, LSM_NPARAM)
+    F = _i32(flags).reshape(-1, LSM_NFLAG)
+    S = _f64(step)
+    B = P.shape[0]
+    if F.shape[0] != B or S.ndim != 3 or S.shape[0] != B or S.shape[2] != LSM_NSTEP:
+        raise ValueError("mc_lsm_batch: params [B, 4], flags [B, 3], step [B, n_steps, 9]")
+    n_steps, G = S.shape[1], int(G)
+    stats = np.empty((B, LSM_NSTAT), dtype=np.float64)
+    val = np.empty((B, G * LSM_SUBRUN), dtype=np.float64) if want_values else None
+    coef = np.empty((B, G, n_steps, LSM_NCOEF), dtype=np.float64) if want_coef else None
+    _check(lib().fdcn_mc_lsm_batch(
+        B, n_steps, G, 1 if antithetic else 0, P.ctypes.data, F.ctypes.data, S.ctypes.data,
+        int(seed) & (2 ** 64 - 1), int(obs_first), stats.ctypes.data,
+        val.ctypes.data if want_values else None, coef.ctypes.data if want_coef else None))
+    return stats, val, coef
+
+
+def mc_lsm_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, params_ptr: int,
+                     flags_ptr: int, step_ptr: int, seed: int, obs_first: int, stats_ptr: int,
+                     values_ptr: Optional[int], coef_ptr: Optional[int],
+                     workspace_ptr: Optional[int], workspace_bytes: int,
+                     stream_ptr: Optional[int]) -> None:
+    """fdcn_mc_lsm_batch_dev: every array already on the device; asynchronous
+    on `stream_ptr`."""
+    _check(lib().fdcn_mc_lsm_batch_dev(
+        int(B), int(n_steps), int(G), 1 if antithetic else 0, params_ptr, flags_ptr, step_ptr,
+        int(seed) & (2 ** 64 - 1), int(obs_first), stats_ptr, values_ptr, coef_ptr, workspace_ptr,
+        int(workspace_bytes), stream_ptr))

@@ -1,0 +1,589 @@
+"""Least-squares Monte Carlo (Longstaff-Schwartz) for American and Bermudan
+options with discretely monitored barriers: the independent statistical
+cross-check of the early-exercise FD pricers (american.py,
+american_barrier.py, american_knockin.py), as mc_barrier.py is of the
+European barrier engines.
+
+The events are the FD pricers' own.  A knock-out path ends at its first
+monitored breach h (``s <= lower`` or ``s >= upper``) with
+``max(payoff, R)`` paid there -- the exercise floor of american_barrier.py,
+R = barrier.rebate_value -- and may be exercised before it.  A knock-in path
+may be exercised from its hit step on, that step included, and is paid the
+rebate at maturity if it never knocked in (american_knockin.py); ``rebate_at_hit``
+is refused there as the FD class refuses it.  Voluntary exercise happens on
+the steps flagged EXERCISE only (Bermudan); maturity always exercises.  No
+cash dividends.
+
+The estimator is the out-of-sample one: a sub-run of 4 096 paths fits a
+cubic in the standardised log-spot per exercise date on one path set and
+applies the fitted stopping rule to an independent set.  That is biased low
+(a sub-optimal policy), the sign a cross-check wants; the textbook in-sample
+value is biased high by more than a percent at this fit size and is reported
+as a diagnostic only (``fit_value``).  A contract is G sub-runs; its price is
+the mean of their means and its standard error comes from their spread.
+
+* ``engine="hip"``: libfdcn's kernel (csrc/fdcn_mc_lsm.hip), one workgroup per
+  sub-run, B contracts per launch;
+* ``engine="host"``: NumPy, the same algorithm in the same operation order per
+  path on the same Philox streams (include/fdcn.h), so the two agree path for
+  path up to exp / log and summation order.
+
+A missing GPU under ``engine="hip"`` is an error, never a silent fallback.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+
+from . import capi
+from .barrier import rebate_value
+from .mc_barrier import philox_normals
+
+__all__ = ["LsmContract", "LsmConfig", "plan_american_contract", "contract_from_pricer",
+           "simulate_lsm", "price_american_mc", "mc_american_batch", "merge_lsm_stats"]
+
+_KO = ("down-and-out", "up-and-out", "double-out")
+_KI = ("down-and-in", "up-and-in", "double-in")
+_LOWER = ("down-and-out", "double-out", "down-and-in", "double-in")
+_UPPER = ("up-and-out", "double-out", "up-and-in", "double-in")
+_MERGE = 1e-12  # times closer than this are one step
+_THREADS = 256
+
+
+@dataclass
+class LsmContract:
+    """One contract as the engines take it (include/fdcn.h, fdcn_mc_lsm_*)."""
+    params: np.ndarray   # [LSM_NPARAM]
+    flags: np.ndarray    # [LSM_NFLAG] int32 (stream id 0; set per launch)
+    step: np.ndarray     # [n_steps, LSM_NSTEP]
+    times: np.ndarray    # [n_steps] t_m
+    barrier_type: str
+    fixed_price: Optional[float] = None  # answered without a launch (contract_from_pricer)
+
+    @property
+    def n_steps(self) -> int:
+        return self.step.shape[0]
+
+
+@dataclass(frozen=True)
+class LsmConfig:
+    n_subruns: int = 32
+    antithetic: bool = True
+    seed: int = 42
+
+
+def _step_grid(T: float, exercise: Sequence[float], monitor: Sequence[float]):
+    """Sorted union of the exercise and monitor times in (0, T] and T itself,
+    times within _MERGE of each other merged (into T at the end); the flags."""
+    marks = [(float(t), 0) for t in exercise] + [(float(t), 1) for t in monitor] + [(T, 2)]
+    marks = sorted((T if abs(t - T) <= _MERGE else t, w) for t, w in marks
+                   if 0.0 < t <= T + _MERGE)
+    times: List[float] = []
+    flags: List[List[bool]] = []
+    for t, w in marks:
+        if not times or t - times[-1] > _MERGE:
+            times.append(t)
+            flags.append([False, False])
+        if w < 2:
+            flags[-1][w] = True
+    return np.array(times), np.array(flags, dtype=bool)
+
+
+def plan_american_contract(*, spot: float, strike: float, vol: float, option_type: str,
+                           discount_rate: float, carry_rate: float, time_to_expiry: float,
+                           barrier_type: str = "none", lower_barrier: Optional[float] = None,
+                           upper_barrier: Optional[float] = None,
+                           monitor_times: Sequence[float] = (), rebate_amount: float = 0.0,
+                           rebate_at_hit: bool = False, n_exercise: int = 64,
+                           exercise_times: Optional[Sequence[float]] = None,
+                           dividends: Sequence = ()) -> LsmContract:
+    """Everything the engines need for one contract: the checks, the step grid
+    (the sorted union of k T / n_exercise, or `exercise_times`, and the
+    monitor times in (0, T]) and the per-step table.  Rates are continuously
+    compounded; times are year fractions from valuation."""
+    if len(dividends):
+        raise ValueError("cash dividends are not supported by the least-squares Monte Carlo.")
+    if not (spot > 0.0 and strike > 0.0):
+        raise ValueError("spot and strike must be positive.")
+    if not vol > 0.0:
+        raise ValueError("vol must be positive.")
+    T = float(time_to_expiry)
+    if not T > 0.0:
+        raise ValueError("time_to_expiry must be positive.")
+    if option_type not in ("call", "put"):
+        raise ValueError("option_type must be 'call' or 'put'.")
+    bt = str(barrier_type).lower()
+    if bt not in capi.LSM_KIND:
+        raise ValueError(f"unknown barrier_type {barrier_type!r}")
+    if bt in _KI and rebate_at_hit:
+        raise ValueError("rebate_at_hit=True: a knock-in rebate is paid at maturity, if the "
+                         "option never knocked in.")
+    if bt in _LOWER and not (lower_barrier is not None and lower_barrier > 0.0):
+        raise ValueError(f"{bt} needs a positive lower_barrier.")
+    if bt in _UPPER and not (upper_barrier is not None and upper_barrier > 0.0):
+        raise ValueError(f"{bt} needs a positive upper_barrier.")
+    if bt in _LOWER and bt in _UPPER and not lower_barrier < upper_barrier:
+        raise ValueError("lower_barrier must be below upper_barrier.")
+    if exercise_times is None:
+        n_ex = int(n_exercise)
+        if n_ex < 0:
+            raise ValueError("n_exercise must be >= 0.")
+        exercise_times = [k * T / n_ex for k in range(1, n_ex + 1)]
+    times, fl = _step_grid(T, exercise_times, monitor_times if bt != "none" else ())
+    M = times.shape[0]
+    if M > capi.LSM_MAX_STEPS:
+        raise ValueError(f"{M} steps: the least-squares Monte Carlo takes at most "
+                         f"{capi.LSM_MAX_STEPS}.")
+    r, q = float(discount_rate), float(carry_rate)
+    S = np.zeros((M, capi.LSM_NSTEP))
+    x0 = math.log(spot)
+    prev, sum_drift, sum_var = 0.0, 0.0, 0.0
+    for m in range(M):
+        t = float(times[m])
+        dt = t - prev
+        drift = (q - 0.5 * vol * vol) * dt
+        diff = vol * math.sqrt(dt)
+        sum_drift += drift
+        sum_var += diff * diff
+        S[m, capi.LSM_S_DRIFT] = drift
+        S[m, capi.LSM_S_DIFF] = diff
+        S[m, capi.LSM_S_DF_STEP] = math.exp(-r * dt)
+        S[m, capi.LSM_S_DF_END] = math.exp(-r * t)
+        S[m, capi.LSM_S_EXERCISE] = 1.0 if fl[m, 0] else 0.0
+        S[m, capi.LSM_S_MONITOR] = 1.0 if fl[m, 1] else 0.0
+        if bt != "none":
+            S[m, capi.LSM_S_REBATE] = rebate_value(float(rebate_amount),
+                                                   bool(rebate_at_hit) and bt in _KO, q, T - t)
+        S[m, capi.LSM_S_CENTRE] = x0 + sum_drift
+        S[m, capi.LSM_S_ISCALE] = 1.0 / math.sqrt(sum_var)
+        prev = t
+    params = np.array([spot, strike, lower_barrier if bt in _LOWER else 0.0,
+                       upper_barrier if bt in _UPPER else 0.0], dtype=float)
+    flags = np.array([option_type == "put", capi.LSM_KIND[bt], 0], dtype=np.int32)
+    return LsmContract(params=params, flags=flags, step=S, times=times, barrier_type=bt)
+
+
+def contract_from_pricer(p, n_exercise: int = 64) -> LsmContract:
+    """The contract an AmericanFDMPricer, AmericanBarrierFDMPricer or
+    AmericanKnockInFDMPricer prices: its snapped spot and strike (the FD price
+    is the price at those), sigma, the continuously compounded discount and
+    carry rates, the barrier keywords and the monitoring times of
+    `_monitor_taus`.  A pricer with a dividend in (valuation, maturity] is
+    refused.  An `already_hit` pricer, and a knock-in that can never knock in,
+    carry the pricer's own answer in `fixed_price` and are never launched; an
+    `already_in` pricer is the vanilla contract."""
+    if p._div_times_tau():
+        raise ValueError("cash dividends are not supported by the least-squares Monte Carlo.")
+    if p.spot_snapped is None and p.strike_snapped is None:
+        p._build_log_grid()
+    spot = p.spot_snapped if p.snap_spot_to_grid and p.spot_snapped is not None else p.spot
+    T = p.time_to_expiry
+    bt = getattr(p, "barrier_type", "none")
+    fixed = None
+    if bt in _KO and p.already_hit:
+        fixed = float(p.rebate_amount)
+    elif bt in _KI and p.already_in:
+        bt = "none"
+    elif bt in _KI and p._skip_solve():
+        fixed = float(p._never_in()["price"])
+    mon: List[float] = []
+    if bt != "none":
+        taus, at_maturity = p._monitor_taus()
+        mon = sorted(T - tau for tau in taus) + ([T] if at_maturity else [])
+    c = plan_american_contract(
+        spot=float(spot), strike=float(p._strike_for_pde()), vol=p.sigma,
+        option_type=p.option_type, discount_rate=p.discount_rate_nacc,
+        carry_rate=p.carry_rate_nacc, time_to_expiry=T, barrier_type=bt,
+        lower_barrier=getattr(p, "lower_barrier", None) if bt in _LOWER else None,
+        upper_barrier=getattr(p, "upper_barrier", None) if bt in _UPPER else None,
+        monitor_times=mon, rebate_amount=getattr(p, "rebate_amount", 0.0),
+        rebate_at_hit=getattr(p, "rebate_at_hit", False) and bt in _KO, n_exercise=n_exercise)
+    c.fixed_price = fixed
+    return c
+
+
+# ---------------------------------------------------------------------------
+# the host engine
+# ---------------------------------------------------------------------------
+def obs_per_subrun(antithetic: bool) -> int:
+    return capi.LSM_SUBRUN // 2 if antithetic else capi.LSM_SUBRUN
+
+
+def _path_normals(n_steps: int, seed: int, word: int, obs_first: int, antithetic: bool):
+    """z [LSM_SUBRUN, n_steps] of one sub-run, in path order (include/fdcn.h:
+    path p is slot k = p / 256 of thread p % 256)."""
+    z = philox_normals(obs_per_subrun(antithetic), n_steps, seed, word, obs_first)
+    if not antithetic:
+        return z
+    p = np.arange(capi.LSM_SUBRUN)
+    k, tid = p // _THREADS, p % _THREADS
+    return z[(k // 2) * _THREADS + tid] * np.where(k % 2 == 1, -1.0, 1.0)[:, None]
+
+
+def _cholesky_cubic(sm: np.ndarray):
+    """The kernel's unpivoted 4 x 4 Cholesky on the rows of sm [g, 12], in its
+    operation order -> (c [g, 4], valid [g])."""
+    s = [sm[:, k] for k in range(7)]
+    t = [sm[:, 7 + k] for k in range(4)]
+    tol = 1e-12
+    with np.errstate(all="ignore"):
+        ok = sm[:, 11] >= float(capi.LSM_MIN_FIT)
+        d0 = s[0]
+        ok = ok & (d0 > tol * s[0])
+        l00 = np.sqrt(d0)
+        l10, l20, l30 = s[1] / l00, s[2] / l00, s[3] / l00
+        d1 = s[2] - l10 * l10
+        ok = ok & (d1 > tol * s[2])
+        l11 = np.sqrt(d1)
+        l21, l31 = (s[3] - l20 * l10) / l11, (s[4] - l30 * l10) / l11
+        d2 = s[4] - l20 * l20 - l21 * l21
+        ok = ok & (d2 > tol * s[4])
+        l22 = np.sqrt(d2)
+        l32 = (s[5] - l30 * l20 - l31 * l21) / l22
+        d3 = s[6] - l30 * l30 - l31 * l31 - l32 * l32
+        ok = ok & (d3 > tol * s[6])
+        l33 = np.sqrt(d3)
+        y0 = t[0] / l00
+        y1 = (t[1] - l10 * y0) / l11
+        y2 = (t[2] - l20 * y0 - l21 * y1) / l22
+        y3 = (t[3] - l30 * y0 - l31 * y1 - l32 * y2) / l33
+        c3 = y3 / l33
+        c2 = (y2 - l32 * c3) / l22
+        c1 = (y1 - l21 * c2 - l31 * c3) / l11
+        c0 = (y0 - l10 * c1 - l20 * c2 - l30 * c3) / l00
+    c = np.stack([c0, c1, c2, c3], axis=1)
+    c[~ok] = 0.0
+    return c, ok
+
+
+def _cubic(c: np.ndarray, u: np.ndarray) -> np.ndarray:
+    c0, c1, c2, c3 = (c[:, k][:, None] for k in range(4))
+    return c0 + u * (c1 + u * (c2 + u * c3))
+
+
+def host_subruns(c: LsmContract, subruns: Sequence[int], antithetic: bool, seed: int,
+                 stream_id: int, *, want_fit: bool = False) -> dict:
+    """The sub-runs `subruns` of contract c on the host: the kernel's three
+    phases on arrays [g, LSM_SUBRUN].  -> values [g, LSM_SUBRUN] (price set),
+    fit_mean [g], coef [g, n_steps, LSM_NCOEF], invalid [g], margin [g]; with
+    want_fit also fit_u [g, n_steps, LSM_SUBRUN], the regressor of the paths of
+    each fit (NaN elsewhere)."""
+    P, F, S = c.params, c.flags, c.step
+    M, ng, n = c.n_steps, len(subruns), capi.LSM_SUBRUN
+    strike, lower, upper = float(P[capi.LSM_P_STRIKE]), float(P[capi.LSM_P_LOWER]), \
+        float(P[capi.LSM_P_UPPER])
+    put, kind = bool(F[capi.LSM_F_PUT]), int(F[capi.LSM_F_KIND])
+    ko, ki = 1 <= kind <= 3, kind >= 4
+    has_lo, has_hi = kind in (1, 3, 4, 6), kind in (2, 3, 5, 6)
+    x0 = float(np.log(P[capi.LSM_P_SPOT]))
+    per = obs_per_subrun(antithetic)
+
+    def payoff(s):
+        return np.maximum(strike - s, 0.0) if put else np.maximum(s - strike, 0.0)
+
+    def breach(s):
+        out = np.zeros(s.shape, dtype=bool)
+        if has_lo:
+            out |= s <= lower
+        if has_hi:
+            out |= s >= upper
+        return out
+
+    def normals(word):
+        return np.stack([_path_normals(M, seed, word, int(g) * per, antithetic) for g in subruns])
+
+    drift, diff = S[:, capi.LSM_S_DRIFT], S[:, capi.LSM_S_DIFF]
+    mon = (S[:, capi.LSM_S_MONITOR] != 0.0) & (kind != 0)
+    exr = S[:, capi.LSM_S_EXERCISE] != 0.0
+    exr[M - 1] = False  # maturity is not a fitted step
+    reb, dfs, dfe = S[:, capi.LSM_S_REBATE], S[:, capi.LSM_S_DF_STEP], S[:, capi.LSM_S_DF_END]
+    centre, iscale = S[:, capi.LSM_S_CENTRE], S[:, capi.LSM_S_ISCALE]
+
+    # ---- A: fit set forward
+    Z = normals(2 * int(stream_id))
+    x = np.full((ng, n), x0)
+    h = np.full((ng, n), M + 1, dtype=np.int64)
+    for m in range(1, M + 1):
+        i = m - 1
+        x = x + (drift[i] + diff[i] * Z[:, :, i])
+        if mon[i]:
+            h = np.where(breach(np.exp(x)) & (h > M), m, h)
+
+    # ---- B: fit set backward
+    coef = np.zeros((ng, M, capi.LSM_NCOEF))
+    invalid = np.zeros(ng, dtype=np.int64)
+    margin = np.full(ng, np.inf)
+    fit_u = np.full((ng, M, n), np.nan) if want_fit else None
+    cf = np.zeros((ng, n))
+    for m in range(M, 0, -1):
+        i = m - 1
+        if m == M or exr[i] or (ko and mon[i]):
+            phi = payoff(np.exp(x))
+            u = (x - centre[i]) * iscale[i]
+            if m == M:
+                if ko:
+                    cf = np.where(h == m, np.maximum(phi, reb[i]), phi)
+                elif ki:
+                    cf = np.where(h <= m, phi, reb[i])
+                else:
+                    cf = phi.copy()
+            elif ko:
+                cf = np.where(h == m, np.maximum(phi, reb[i]), cf)
+            if exr[i]:
+                elig = (m < h) if ko else ((m >= h) if ki else np.ones((ng, n), dtype=bool))
+                part = elig & (phi > 0.0)
+                u2 = u * u
+                u3 = u2 * u
+                terms = [np.ones_like(u), u, u2, u3, u2 * u2, u3 * u2, u3 * u3, cf, u * cf,
+                         u2 * cf, u3 * cf, np.ones_like(u)]
+                sm = np.stack([np.sum(np.where(part, t, 0.0), axis=1) for t in terms], axis=1)
+                cc, valid = _cholesky_cubic(sm)
+                fit = _cubic(cc, u)
+                take = part & valid[:, None]
+                if take.any():
+                    gap = np.where(take, np.abs(phi - fit), np.inf)
+                    margin = np.minimum(margin, gap.min(axis=1))
+                cf = np.where(take & (phi > fit), phi, cf)
+                invalid += ~valid
+                coef[:, i, :4] = cc
+                coef[:, i, 4] = valid
+                if want_fit:
+                    fit_u[:, i, :] = np.where(take, u, np.nan)
+        x = x - (drift[i] + diff[i] * Z[:, :, i])
+        cf = cf * dfs[i]
+    fit_mean = np.sum(cf, axis=1) / float(n)
+
+    # ---- C: price set forward
+    Z = normals(2 * int(stream_id) + 1)
+    x = np.full((ng, n), x0)
+    val = np.zeros((ng, n))
+    done = np.zeros((ng, n), dtype=bool)
+    inn = np.zeros((ng, n), dtype=bool)
+    for m in range(1, M + 1):
+        i = m - 1
+        x = x + (drift[i] + diff[i] * Z[:, :, i])
+        fitted = (coef[:, i, 4] != 0.0)[:, None] & bool(exr[i])
+        if not (mon[i] or m == M or fitted.any()):
+            continue
+        s = np.exp(x)
+        phi = payoff(s)
+        hit = breach(s) if mon[i] else np.zeros((ng, n), dtype=bool)
+        if ko:
+            k = hit & ~done
+            val = np.where(k, np.maximum(phi, reb[i]) * dfe[i], val)
+            done |= k
+        if ki:
+            inn |= hit
+        elig = inn if ki else np.ones((ng, n), dtype=bool)
+        if m == M:
+            val = np.where(~done, np.where(elig, phi, reb[i]) * dfe[i], val)
+            done[:] = True
+        else:
+            cand = ~done & fitted & elig & (phi > 0.0)
+            if cand.any():
+                u = (x - centre[i]) * iscale[i]
+                fit = _cubic(coef[:, i, :4], u)
+                gap = np.where(cand, np.abs(phi - fit), np.inf)
+                margin = np.minimum(margin, gap.min(axis=1))
+                go = cand & (phi > fit)
+                val = np.where(go, phi * dfe[i], val)
+                done |= go
+    out = dict(values=val, fit_mean=fit_mean, coef=coef, invalid=invalid, margin=margin)
+    if want_fit:
+        out["fit_u"] = fit_u
+    return out
+
+
+def _finalize(means: np.ndarray, fit_means: np.ndarray, invalid: float, margin: float):
+    """One row of stats [LSM_NSTAT] from the sub-run means, the finalize
+    kernel's formulas."""
+    G = means.shape[0]
+    n = float(G)
+    s, s2 = float(np.sum(means)), float(np.sum(means * means))
+    f, f2 = float(np.sum(fit_means)), float(np.sum(fit_means * fit_means))
+
+    def se(a, a2):
+        return math.sqrt(max(0.0, a2 - a * a / n) / (n - 1.0) / n) if G > 1 else 0.0
+    return np.array([s / n, se(s, s2), f / n, se(f, f2), s, s2, float(invalid), float(margin)])
+
+
+def merge_lsm_stats(parts) -> Dict[str, float]:
+    """Price and standard error of the union of disjoint sub-run ranges of one
+    contract, from their (G, sum, sum of squares) of the sub-run means --
+    tuples, or the result dicts of mc_american_batch.  Ranks that shard a
+    contract's sub-runs (subrun_range) gather these three numbers, as
+    merge_mc_stats does for observations."""
+    G, s, s2 = 0, 0.0, 0.0
+    for part in parts:
+        if isinstance(part, dict):
+            part = (part["n_subruns"], part["sum_mean"], part["sum_mean2"])
+        G += int(part[0])
+        s += float(part[1])
+        s2 += float(part[2])
+    if G <= 0:
+        raise ValueError("merge_lsm_stats: no sub-runs")
+    n = float(G)
+    stderr = math.sqrt(max(0.0, s2 - s * s / n) / (n - 1.0) / n) if G > 1 else 0.0
+    return {"price": s / n, "stderr": stderr, "n_subruns": G, "sum_mean": s, "sum_mean2": s2}
+
+
+def _stack(group: Sequence[LsmContract], stream_ids: Sequence[int]):
+    P = np.stack([c.params for c in group])
+    F = np.stack([c.flags for c in group]).astype(np.int32)
+    F[:, capi.LSM_F_STREAM] = np.asarray(stream_ids, dtype=np.int32)
+    S = np.stack([c.step for c in group])
+    return P, F, S
+
+
+def simulate_lsm(group: Sequence[LsmContract], n_subruns: int, antithetic: bool, *,
+                 engine: str = "hip", seed: int = 0, stream_ids: Optional[Sequence[int]] = None,
+                 subrun_first: int = 0, want_values: bool = False, want_coef: bool = False,
+                 host_chunk: int = 16) -> dict:
+    """Run sub-runs subrun_first .. subrun_first + n_subruns - 1 of contracts
+    that share n_steps.  -> {"stats": [B, LSM_NSTAT]} plus "values"
+    [B, n_subruns * LSM_SUBRUN] and "coef" [B, n_subruns, n_steps, LSM_NCOEF]
+    where asked for.  The Philox stream id of a contract is its index in
+    `group`, or stream_ids[index]."""
+    if engine not in ("hip", "host"):
+        raise ValueError("engine must be 'hip' or 'host'")
+    B = len(group)
+    if B < 1:
+        raise ValueError("simulate_lsm: no contracts")
+    n_steps = group[0].n_steps
+    if any(c.n_steps != n_steps for c in group):
+        raise ValueError("simulate_lsm: the contracts of a launch share n_steps")
+    if n_steps > capi.LSM_MAX_STEPS:
+        raise ValueError(f"simulate_lsm: at most {capi.LSM_MAX_STEPS} steps")
+    G = int(n_subruns)
+    if G < 1:
+        raise ValueError("simulate_lsm: n_subruns must be >= 1")
+    first = int(subrun_first)
+    if first != subrun_first or first < 0:
+        raise ValueError("simulate_lsm: subrun_first must be a whole, non-negative number of "
+                         "sub-runs (a shard starts on a sub-run)")
+    ids = list(range(B)) if stream_ids is None else [int(s) for s in stream_ids]
+    if len(ids) != B:
+        raise ValueError("simulate_lsm: one stream id per contract")
+    if any(not 0 <= s < 2 ** 30 for s in ids):
+        raise ValueError("simulate_lsm: stream ids must be in 0 .. 2^30 - 1")
+    antithetic = bool(antithetic)
+    if engine == "hip":
+        capi.require_device()
+        P, F, S = _stack(group, ids)
+        stats, val, coef = capi.mc_lsm_batch(P, F, S, G, antithetic, seed=seed,
+                                             obs_first=first * obs_per_subrun(antithetic),
+                                             want_values=want_values, want_coef=want_coef)
+        out = {"stats": stats}
+        if want_values:
+            out["values"] = val
+        if want_coef:
+            out["coef"] = coef
+        return out
+    stats = np.empty((B, capi.LSM_NSTAT))
+    val = np.empty((B, G * capi.LSM_SUBRUN)) if want_values else None
+    coef = np.empty((B, G, n_steps, capi.LSM_NCOEF)) if want_coef else None
+    for b, c in enumerate(group):
+        means, fits = np.empty(G), np.empty(G)
+        invalid, margin = 0, math.inf
+        for lo in range(0, G, max(1, int(host_chunk))):
+            hi = min(G, lo + max(1, int(host_chunk)))
+            r = host_subruns(c, range(first + lo, first + hi), antithetic, seed, ids[b])
+            means[lo:hi] = np.sum(r["values"], axis=1) / float(capi.LSM_SUBRUN)
+            fits[lo:hi] = r["fit_mean"]
+            invalid += int(r["invalid"].sum())
+            margin = min(margin, float(r["margin"].min()))
+            if want_values:
+                val[b, lo * capi.LSM_SUBRUN:hi * capi.LSM_SUBRUN] = r["values"].reshape(-1)
+            if want_coef:
+                coef[b, lo:hi] = r["coef"]
+        stats[b] = _finalize(means, fits, invalid, margin)
+    out = {"stats": stats}
+    if want_values:
+        out["values"] = val
+    if want_coef:
+        out["coef"] = coef
+    return out
+
+
+def _result(c: LsmContract, cfg: LsmConfig, G: int, st: Optional[np.ndarray]) -> dict:
+    if st is None:  # answered by the pricer's own rule, nothing simulated
+        price = float(c.fixed_price)
+        st = np.array([price, 0.0, price, 0.0, price * G, price * price * G, 0.0, math.inf])
+        n_paths = 0
+    else:
+        n_paths = G * capi.LSM_SUBRUN
+    price, stderr = float(st[capi.LSM_O_PRICE]), float(st[capi.LSM_O_STDERR])
+    return {
+        "price": price,
+        "stderr": stderr,
+        "ci_95": (price - 1.96 * stderr, price + 1.96 * stderr),
+        "fit_value": float(st[capi.LSM_O_FIT_VALUE]),
+        "fit_stderr": float(st[capi.LSM_O_FIT_STDERR]),
+        "n_paths": int(n_paths),
+        "n_subruns": int(G),
+        "steps": int(c.n_steps),
+        "invalid_fit_steps": int(st[capi.LSM_O_INVALID]),
+        "min_margin": float(st[capi.LSM_O_MIN_MARGIN]),
+        "barrier_type": c.barrier_type,
+        "sum_mean": float(st[capi.LSM_O_SUM]),
+        "sum_mean2": float(st[capi.LSM_O_SUM2]),
+    }
+
+
+def mc_american_batch(contracts: Sequence, cfg: LsmConfig = LsmConfig(), *, engine: str = "hip",
+                      stream_ids: Optional[Sequence[int]] = None,
+                      subrun_range: Optional[range] = None) -> List[dict]:
+    """Price many contracts, one launch per distinct step count.  `contracts`:
+    LsmContract objects, or the keyword arguments of plan_american_contract per
+    contract; cfg is shared.  The Philox stream id of a contract is its index
+    in `contracts`, or stream_ids[index].  `subrun_range` (a contiguous range
+    within [0, cfg.n_subruns)) runs that part of every contract's sub-runs only
+    -- a rank's shard -- and merge_lsm_stats combines the parts.  Results, in
+    input order: price_american_mc's dict plus "sum_mean" and "sum_mean2"."""
+    plans = [c if isinstance(c, LsmContract) else plan_american_contract(**c) for c in contracts]
+    lo, hi = 0, int(cfg.n_subruns)
+    if hi < 1:
+        raise ValueError("cfg.n_subruns must be positive.")
+    if subrun_range is not None:
+        lo, hi = subrun_range.start, subrun_range.stop
+        if subrun_range.step != 1 or not 0 <= lo < hi <= cfg.n_subruns:
+            raise ValueError("subrun_range must be a non-empty contiguous range within the "
+                             "contract's sub-runs")
+    ids = list(range(len(plans))) if stream_ids is None else [int(s) for s in stream_ids]
+    if len(ids) != len(plans):
+        raise ValueError("one stream id per contract")
+    out: List[Optional[dict]] = [None] * len(plans)
+    by_steps: Dict[int, List[int]] = {}
+    for k, c in enumerate(plans):
+        if c.fixed_price is not None:
+            out[k] = _result(c, cfg, hi - lo, None)
+        else:
+            by_steps.setdefault(c.n_steps, []).append(k)
+    for members in by_steps.values():
+        r = simulate_lsm([plans[k] for k in members], hi - lo, cfg.antithetic, engine=engine,
+                         seed=cfg.seed, stream_ids=[ids[k] for k in members], subrun_first=lo)
+        for row, k in enumerate(members):
+            out[k] = _result(plans[k], cfg, hi - lo, r["stats"][row])
+    return out  # type: ignore[return-value]
+
+
+def price_american_mc(contract: Optional[LsmContract] = None, *, n_subruns: int = 32,
+                      antithetic: bool = True, seed: int = 42, stream_id: int = 0,
+                      engine: str = "hip", **plan_kw) -> Dict[str, object]:
+    """Least-squares Monte Carlo price of one contract -- an LsmContract
+    (contract_from_pricer), or the keyword arguments of plan_american_contract
+    -- on the chosen engine.  Keys: price (the out-of-sample estimate), stderr,
+    ci_95, fit_value and fit_stderr (the in-sample estimate, a diagnostic),
+    n_paths, n_subruns, steps, invalid_fit_steps, min_margin, barrier_type."""
+    if contract is None:
+        contract = plan_american_contract(**plan_kw)
+    elif plan_kw:
+        raise TypeError("give a contract or the keywords of plan_american_contract, not both")
+    cfg = LsmConfig(n_subruns=int(n_subruns), antithetic=bool(antithetic), seed=int(seed))
+    res = mc_american_batch([contract], cfg, engine=engine, stream_ids=[stream_id])[0]
+    res.pop("sum_mean")
+    res.pop("sum_mean2")
+    return res

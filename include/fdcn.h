@@ -48,7 +48,9 @@ extern "C" {
 /* 8: fdcn_session_upload, fdcn_session_knockout and fdcn_session_march_ps (the
  * American knock-out chain: monitoring events between IT segments) were added
  * after 7; fdcn_session_knockin (the American knock-in chain) joined later as
- * an additive symbol, with the version left at 8.
+ * an additive symbol, with the version left at 8.  So did the least-squares
+ * Monte Carlo entry points (fdcn_mc_lsm_batch, fdcn_mc_lsm_batch_dev,
+ * fdcn_mc_lsm_plan).
  * 7: the BGK barrier pricer's Monte Carlo entry points (fdcn_mc_bgk_batch,
  * fdcn_mc_bgk_batch_dev, fdcn_mc_bgk_plan) were added after 6.
  * 6: the Monte Carlo discrete-barrier entry points (fdcn_mc_barrier_batch,
@@ -584,6 +586,137 @@ int fdcn_mc_bgk_batch_dev(int32_t B, int32_t G, int32_t n_steps, int64_t n_obs,
  * bytes per trade.  Any output pointer may be NULL.  Host only. */
 int fdcn_mc_bgk_plan(int64_t n_obs, int32_t G, int32_t* blocks_per_trade, int32_t* obs_per_block,
                      int64_t* ws_bytes_per_trade);
+
+/* ---- Least-squares Monte Carlo for American / Bermudan options with discrete
+ * barriers (csrc/fdcn_mc_lsm.hip): the statistical cross-check of the
+ * early-exercise FD pricers (Longstaff-Schwartz, out-of-sample estimator).
+ * One launch prices B contracts that share n_steps, G and `antithetic`.
+ *   params[B][FDCN_LSM_NPARAM]          see enum fdcn_lsm_param
+ *   flags [B][FDCN_LSM_NFLAG]           see enum fdcn_lsm_flag
+ *   step  [B][n_steps][FDCN_LSM_NSTEP]  see enum fdcn_lsm_step; row m - 1 is
+ *                                       step m = 1 .. n_steps, ending at t_m
+ * A contract is G sub-runs; one workgroup owns one sub-run: FDCN_LSM_SUBRUN
+ * paths, a complete LSM of its own (fit, then price on fresh paths).  Path p
+ * of a sub-run is slot k = p / 256 of thread p % 256.  Without antithetic
+ * path p is observation p; with it a sub-run has FDCN_LSM_SUBRUN / 2
+ * observations, path p is observation (k / 2) * 256 + p % 256 with +z for k
+ * even and -z for k odd.  Every operation below is rounded separately.
+ *
+ * A, fit set forward: x = ln(spot); x += DRIFT_m + DIFF_m * z_m for m = 1 ..
+ * n_steps; s = exp(x); h = the first MONITOR step with s <= lower (kinds with
+ * a lower level) or s >= upper (kinds with an upper level), n_steps + 1 if
+ * none.
+ * B, fit set backward, m = n_steps .. 1, x and the payoff phi = max(+-(exp(x)
+ * - strike), 0) at t_m, cf the realised cashflow discounted to t_m:
+ *   m = n_steps   knock-out: cf = max(phi, REBATE_m) if h == m, phi if h > m;
+ *                 knock-in:  cf = phi if h <= m, else REBATE_m;  none: phi.
+ *   m < n_steps   x -= DRIFT_{m+1} + DIFF_{m+1} * z_{m+1}, cf *= DF_STEP_{m+1};
+ *                 a knock-out path with h == m: cf = max(phi, REBATE_m) (the
+ *                 exercise floor of the FD knock-out); then, on an EXERCISE
+ *                 step, the eligible paths (knock-out: m < h, knock-in: m >= h,
+ *                 none: all) with phi > 0 enter a cubic least-squares fit of
+ *                 cf on u = (x - CENTRE_m) * ISCALE_m: the twelve sums
+ *                 sum u^0 .. u^6, sum u^k cf (k = 0 .. 3) and the count, each
+ *                 thread in slot order, then a fixed tree; an unpivoted 4 x 4
+ *                 Cholesky in a fixed order on every lane.  The fit is invalid
+ *                 with fewer than FDCN_LSM_MIN_FIT paths or a pivot d_j <=
+ *                 1e-12 * a_jj: no voluntary exercise at that step.  Otherwise
+ *                 fit(u) = c0 + u (c1 + u (c2 + u c3)) and a path of the fit
+ *                 exercises where phi > fit(u), strictly: cf = phi.
+ *   The in-sample value of a path is cf * DF_STEP_1.
+ * C, price set forward (independent normals): the path stops at the first
+ * step where the event rule (knock-out breach: max(phi, REBATE_m); maturity)
+ * or the fitted rule (EXERCISE step, valid fit, eligible, phi > 0, phi >
+ * fit(u)) says so; its value is the cashflow times DF_END_m.  A knock-in
+ * breach at step m makes the path eligible from m on, m included.
+ *
+ * Normals: the Philox mapping of fdcn_mc_barrier_batch with counter word 3 =
+ * 2 * stream id (fit set) or 2 * stream id + 1 (price set), stream id < 2^30:
+ *   counter = (o low, o high, pair, stream word), key = seed,
+ *   o = obs_first + g * (observations per sub-run) + i for observation i of
+ *   sub-run g.  obs_first must be a multiple of the observations per sub-run:
+ *   disjoint sub-run ranges of one (seed, stream id) are shards of one run,
+ *   and their (G, sum, sum of squares) of the sub-run means merge.
+ * Reduction: no floating-point atomics; sums per thread in slot order, a fixed
+ * tree, one partial per sub-run, added in sub-run order by a second kernel.  A
+ * contract's numbers depend on neither B nor its position in the batch.
+ *   stats [B][FDCN_LSM_NSTAT]           see enum fdcn_lsm_stat
+ *   values_out [B][G * FDCN_LSM_SUBRUN] price-set value per path (NULL: none)
+ *   coef_out [B][G][n_steps][FDCN_LSM_NCOEF]  c0 .. c3 and 1.0 / 0.0 for a
+ *                                       valid fit, zeros at steps without a
+ *                                       fit (NULL: none)
+ * Validation (before any device call; FDCN_EINVAL): B, G < 1; n_steps outside
+ * 1 .. FDCN_LSM_MAX_STEPS; B * G beyond a grid; antithetic out of range;
+ * obs_first negative or misaligned; NULL params / flags / step / stats; and,
+ * host entry only: put, kind (0 .. 6) or stream id (0 .. 2^30 - 1) out of
+ * range; spot or strike <= 0; a level <= 0 where the kind reads it, lower >=
+ * upper for a double barrier; a step with DIFF <= 0 (sigma must be positive),
+ * ISCALE <= 0 or a non-finite entry. */
+#define FDCN_LSM_MAX_STEPS 512
+#define FDCN_LSM_SUBRUN 4096
+#define FDCN_LSM_MIN_FIT 64
+#define FDCN_LSM_NCOEF 5
+#define FDCN_LSM_NPARAM 4
+enum fdcn_lsm_param {
+  FDCN_LSM_P_SPOT = 0,
+  FDCN_LSM_P_STRIKE,
+  FDCN_LSM_P_LOWER, /* lower level (kinds 1, 3, 4, 6)                          */
+  FDCN_LSM_P_UPPER  /* upper level (kinds 2, 3, 5, 6)                          */
+};
+#define FDCN_LSM_NFLAG 3
+enum fdcn_lsm_flag {
+  FDCN_LSM_F_PUT = 0, /* 0 call, 1 put                                          */
+  FDCN_LSM_F_KIND,    /* 0 none, 1 down-out, 2 up-out, 3 double-out, 4 down-in,
+                         5 up-in, 6 double-in                                   */
+  FDCN_LSM_F_STREAM   /* Philox stream id, 0 .. 2^30 - 1                        */
+};
+#define FDCN_LSM_NSTEP 9
+enum fdcn_lsm_step {
+  FDCN_LSM_S_DRIFT = 0, /* (carry - sigma^2 / 2) * dt_m                         */
+  FDCN_LSM_S_DIFF,      /* sigma * sqrt(dt_m), > 0                              */
+  FDCN_LSM_S_DF_STEP,   /* discount factor over the step, t_m back to t_{m-1}   */
+  FDCN_LSM_S_DF_END,    /* discount factor from t_m to valuation                */
+  FDCN_LSM_S_MONITOR,   /* 1.0 if t_m is a monitoring time, else 0.0            */
+  FDCN_LSM_S_EXERCISE,  /* 1.0 if the holder may exercise at t_m, else 0.0
+                           (maturity always exercises)                          */
+  FDCN_LSM_S_REBATE,    /* knock-out: paid to a path knocked at t_m; knock-in:
+                           read at maturity only                                */
+  FDCN_LSM_S_CENTRE,    /* ln(spot) + sum of DRIFT up to m                      */
+  FDCN_LSM_S_ISCALE     /* 1 / sqrt(sum of DIFF^2 up to m)                      */
+};
+#define FDCN_LSM_NSTAT 8
+enum fdcn_lsm_stat {
+  FDCN_LSM_O_PRICE = 0,  /* mean of the sub-run out-of-sample means             */
+  FDCN_LSM_O_STDERR,     /* their sample standard deviation / sqrt(G); 0: G = 1 */
+  FDCN_LSM_O_FIT_VALUE,  /* mean of the in-sample means (diagnostic, biased up) */
+  FDCN_LSM_O_FIT_STDERR,
+  FDCN_LSM_O_SUM,        /* sum of the sub-run out-of-sample means (merging)    */
+  FDCN_LSM_O_SUM2,       /* sum of their squares                                */
+  FDCN_LSM_O_INVALID,    /* invalid fit steps, over the G sub-runs              */
+  FDCN_LSM_O_MIN_MARGIN  /* min |phi - fit(u)| over every fit decision taken,
+                            both path sets; +inf if none                        */
+};
+/* Host pointers; copies in and out on the calling thread's stream and waits. */
+int fdcn_mc_lsm_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                      const double* params, const int32_t* flags, const double* step,
+                      uint64_t seed, int64_t obs_first, double* stats, double* values_out,
+                      double* coef_out);
+/* Device pointers, asynchronous on `stream`, no host sync.  `workspace` is
+ * device scratch of at least B * ws_bytes_per_contract (fdcn_mc_lsm_plan)
+ * bytes -- a smaller workspace_bytes is FDCN_EINVAL -- or NULL: allocated
+ * stream-ordered for the call.  The arrays are device memory, so their
+ * contents are not checked here: the kernel treats a KIND outside 0..6 as 0. */
+int fdcn_mc_lsm_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                          const double* params, const int32_t* flags, const double* step,
+                          uint64_t seed, int64_t obs_first, double* stats, double* values_out,
+                          double* coef_out, double* workspace, int64_t workspace_bytes,
+                          void* stream);
+/* Geometry of a launch: observations per sub-run, workspace bytes per
+ * contract, doubles per contract of values_out and of coef_out.  Any output
+ * pointer may be NULL.  Host only. */
+int fdcn_mc_lsm_plan(int32_t n_steps, int32_t G, int32_t antithetic, int32_t* obs_per_subrun,
+                     int64_t* ws_bytes_per_contract, int64_t* values_per_contract,
+                     int64_t* coef_per_contract);
 
 /* ---- host-side plan helpers (no device) -------------------------------- */
 /* Uniform log grid of the pricers' _build_log_grid
