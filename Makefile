@@ -3,7 +3,11 @@
 # Makefile adds the CPU sanitizer runs of SURVEY §5 on libfdcn's host code.
 #
 #   make lib        the in-tree libfdcn.so (same as __graft_entry__.build_lib)
-#   make sanitize   asan + tsan below (CPU only, no GPU needed)
+#   make sanitize   asan + tsan + host_call below (CPU only, no GPU needed)
+#   make host_call  tools/sanitize/host_call_driver.cpp: the staging of the
+#                   host-array entry points (csrc/fdcn_host_call.h) under ASan
+#                   (leak check on) + UBSan, malloc / memcpy standing in for
+#                   the stream-ordered HIP calls, a failure injected at each
 #   make asan       fdcn_host.hip + fdcn_plan.hip (every host entry point that
 #                   runs without a device: plan checks, plan builders, log
 #                   grid, tau sequence, dividend jump, vmath) compiled for the
@@ -29,14 +33,14 @@ TSAN := -Xarch_host -fsanitize=thread
 CSRC := finite_difference_amd/csrc
 HOST_SRCS := $(CSRC)/fdcn_host.hip $(CSRC)/fdcn_plan.hip
 HDRS := include/fdcn.h include/fdcn_diag.h $(CSRC)/fdcn_shared.h $(CSRC)/fdcn_session_book.h \
-        $(CSRC)/fdcn_philox.h
+        $(CSRC)/fdcn_host_call.h $(CSRC)/fdcn_philox.h
 DEV_OBJS := build/obj/fdcn_kernels.o build/obj/fdcn_analytic.o build/obj/fdcn_session.o \
             build/obj/fdcn_vc.o build/obj/fdcn_mc.o build/obj/fdcn_mc_bgk.o \
             build/obj/fdcn_mc_lsm.o
 SAN_TESTS := tests/test_tau_sequence.py tests/test_capi_symbols.py tests/test_scenario_batch.py \
              tests/test_american_batch.py tests/test_barrier_host.py tests/test_american_host.py
 
-.PHONY: lib sanitize asan tsan clean-sanitize
+.PHONY: lib sanitize asan tsan host_call clean-sanitize
 
 lib:
 	$(PY) -c "import __graft_entry__ as g; g.build_lib()"
@@ -76,7 +80,17 @@ build/tsan/plan_driver: build/tsan/plan_driver.o build/tsan/fdcn_host.o build/ts
 tsan: build/tsan/plan_driver
 	TSAN_OPTIONS=halt_on_error=1:second_deadlock_stack=1 ./build/tsan/plan_driver
 
-sanitize: asan tsan
+build/asan/host_call_driver: tools/sanitize/host_call_driver.cpp $(CSRC)/fdcn_host_call.h \
+                             $(CSRC)/fdcn_session_book.h include/fdcn.h
+	@mkdir -p build/asan
+	$(CXX) -std=c++17 -g -O1 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -fno-omit-frame-pointer -o $@ $<
+
+host_call: build/asan/host_call_driver
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
+	    ./build/asan/host_call_driver
+
+sanitize: asan tsan host_call
 
 clean-sanitize:
 	rm -rf build/asan build/tsan

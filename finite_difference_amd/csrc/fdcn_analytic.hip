@@ -22,6 +22,7 @@
 #include <string.h>
 
 #include "../../include/fdcn.h"
+#include "fdcn_shared.h"
 
 namespace {
 
@@ -154,14 +155,6 @@ __global__ void __launch_bounds__(256) double_barrier_kernel(int32_t B, int32_t 
   price[i] = in ? bs - out : out;
 }
 
-}  // namespace
-
-namespace fdcn_internal {
-int set_error(int code, const char* msg);  // fdcn_kernels.hip (fdcn_last_error)
-}
-
-namespace {
-
 int afail(int code, const char* msg) { return fdcn_internal::set_error(code, msg); }
 
 int check_flags(int32_t B, const int32_t* F, int nflag, int maxes0, int maxes1) {
@@ -171,39 +164,6 @@ int check_flags(int32_t B, const int32_t* F, int nflag, int maxes0, int maxes1) 
       return afail(FDCN_EINVAL, "analytic batch: flag out of range");
   }
   return FDCN_OK;
-}
-
-template <typename Launch>
-int host_run(int32_t B, size_t np, size_t nf, size_t nout, const double* P, const int32_t* F,
-             double* out0, double* out1, Launch launch) {
-  if (B == 0) return FDCN_OK;
-  double *dP = nullptr, *dO = nullptr;
-  int32_t* dF = nullptr;
-  const size_t nb = (size_t)B;
-  int rc = FDCN_OK;
-  if (hipMalloc((void**)&dP, sizeof(double) * nb * np) != hipSuccess ||
-      hipMalloc((void**)&dF, sizeof(int32_t) * nb * nf) != hipSuccess ||
-      hipMalloc((void**)&dO, sizeof(double) * nb * nout) != hipSuccess) {
-    rc = afail(FDCN_ENOMEM, "analytic batch: hipMalloc failed");
-  }
-  if (rc == FDCN_OK &&
-      (hipMemcpy(dP, P, sizeof(double) * nb * np, hipMemcpyHostToDevice) != hipSuccess ||
-       hipMemcpy(dF, F, sizeof(int32_t) * nb * nf, hipMemcpyHostToDevice) != hipSuccess))
-    rc = afail(FDCN_EHIP, "analytic batch: H2D copy failed");
-  if (rc == FDCN_OK) {
-    launch(dP, dF, dO, dO + (nout > 1 ? nb : 0), (hipStream_t) nullptr);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-      rc = afail(FDCN_EHIP, "analytic batch: kernel failed");
-  }
-  if (rc == FDCN_OK &&
-      (hipMemcpy(out0, dO, sizeof(double) * nb, hipMemcpyDeviceToHost) != hipSuccess ||
-       (out1 && hipMemcpy(out1, dO + nb, sizeof(double) * nb, hipMemcpyDeviceToHost) !=
-                    hipSuccess)))
-    rc = afail(FDCN_EHIP, "analytic batch: D2H copy failed");
-  if (dP) (void)hipFree(dP);
-  if (dF) (void)hipFree(dF);
-  if (dO) (void)hipFree(dO);
-  return rc;
 }
 
 }  // namespace
@@ -233,11 +193,17 @@ int fdcn_rr_barrier_batch(int32_t B, const double* params, const int32_t* flags,
     if (!(p[5] > 0.0) || !(p[3] > 0.0))
       return afail(FDCN_EINVAL, "rr_barrier_batch: sigma and t must be positive");
   }
-  return host_run(B, FDCN_RR_NPARAM, FDCN_RR_NFLAG, 2, params, flags, price, vanilla,
-                  [&](const double* dP, const int32_t* dF, double* o0, double* o1, hipStream_t s) {
-                    hipLaunchKernelGGL(rr_barrier_kernel, dim3((B + 255) / 256), dim3(256), 0, s,
-                                       B, dP, dF, o0, o1);
-                  });
+  if (B == 0) return FDCN_OK;
+  fdcn_internal::HostCall c("rr_barrier_batch");
+  if ((rc = c.open())) return rc;
+  const int rP = c.in(params, sizeof(double) * (size_t)B * FDCN_RR_NPARAM);
+  const int rF = c.in(flags, sizeof(int32_t) * (size_t)B * FDCN_RR_NFLAG);
+  const int rO = c.out(price, sizeof(double) * (size_t)B);
+  const int rV = c.out(vanilla, sizeof(double) * (size_t)B);
+  return c.run([&](hipStream_t s) {
+    return fdcn_rr_barrier_batch_dev(B, c.dev<double>(rP), c.dev<int32_t>(rF), c.dev<double>(rO),
+                                     c.dev<double>(rV), s);
+  });
 }
 
 int fdcn_double_barrier_batch_dev(int32_t B, int32_t m, const double* params,
@@ -255,11 +221,16 @@ int fdcn_double_barrier_batch(int32_t B, int32_t m, const double* params, const 
     return afail(FDCN_EINVAL, "double_barrier_batch: bad arguments");
   int rc = check_flags(B, flags, FDCN_DB_NFLAG, 1, 1);
   if (rc) return rc;
-  return host_run(B, FDCN_DB_NPARAM, FDCN_DB_NFLAG, 1, params, flags, price, nullptr,
-                  [&](const double* dP, const int32_t* dF, double* o0, double*, hipStream_t s) {
-                    hipLaunchKernelGGL(double_barrier_kernel, dim3((B + 255) / 256), dim3(256),
-                                       0, s, B, m, dP, dF, o0);
-                  });
+  if (B == 0) return FDCN_OK;
+  fdcn_internal::HostCall c("double_barrier_batch");
+  if ((rc = c.open())) return rc;
+  const int rP = c.in(params, sizeof(double) * (size_t)B * FDCN_DB_NPARAM);
+  const int rF = c.in(flags, sizeof(int32_t) * (size_t)B * FDCN_DB_NFLAG);
+  const int rO = c.out(price, sizeof(double) * (size_t)B);
+  return c.run([&](hipStream_t s) {
+    return fdcn_double_barrier_batch_dev(B, m, c.dev<double>(rP), c.dev<int32_t>(rF),
+                                         c.dev<double>(rO), s);
+  });
 }
 
 }  // extern "C"

@@ -3124,11 +3124,61 @@ int launch(int it, int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
   return FDCN_OK;
 }
 
+int host_batch(int it, int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
+               const double* params, const int32_t* iparams, const double* v_init,
+               const double* payoff, int32_t n_mon, const int32_t* mon_step,
+               const double* mon_rebate, double* v_out) {
+  int rc = validate_plan(it, B, n_nodes, n_time, n_ranna, params, iparams, n_mon, mon_step,
+                         mon_rebate);
+  if (rc) return rc;
+  if (B > 0 && (!v_init || !v_out || (it && !payoff)))
+    return fail(FDCN_EINVAL, "null array argument");
+  if (B == 0) return FDCN_OK;
+  const int k_cap = fdcn_sm_extent(B, n_nodes, n_time, n_ranna, params);
+  if (k_cap < 0) return k_cap;
+  fdcn_internal::HostCall c(it ? "fdcn_it_batch" : "fdcn_cn_batch");
+  if ((rc = c.open())) return rc;
+  int32_t w_, npt_, spb_, lds_;
+  int64_t ws_ = 0;
+  rc = fdcn_plan(B, n_nodes, n_time, it, k_cap, &w_, &npt_, &spb_, &lds_, &ws_);
+  if (rc) return rc;
+  const size_t nv = sizeof(double) * (size_t)B * n_nodes;
+  const size_t nm = (size_t)(n_mon > 0 ? n_mon : 1);  // room for one entry without monitors
+  const size_t ws_bytes = (size_t)ws_ * (size_t)B;
+  const int rP = c.in(params, sizeof(double) * (size_t)B * FDCN_NPARAM);
+  const int rI = c.in(iparams, sizeof(int32_t) * (size_t)B * FDCN_NIPARAM);
+  const int rV = c.in(v_init, nv);
+  const int rO = c.out(v_out, nv);
+  const int rF = c.in(it ? payoff : nullptr, nv);
+  const int rM = c.in(mon_step, sizeof(int32_t) * (size_t)n_mon, sizeof(int32_t) * nm);
+  const int rR = c.in(mon_rebate, sizeof(double) * (size_t)n_mon, sizeof(double) * nm);
+  const int rW = c.scratch(ws_bytes);
+  return c.run([&](hipStream_t stream) {
+    return launch(it, B, n_nodes, n_time, n_ranna, c.dev<double>(rP), c.dev<int32_t>(rI),
+                  c.dev<double>(rV), c.dev<double>(rF), n_mon, c.dev<int32_t>(rM),
+                  c.dev<double>(rR), c.dev<double>(rO), k_cap, c.dev<double>(rW),
+                  (int64_t)ws_bytes, stream);
+  });
+}
+
+}  // namespace
+
+namespace fdcn_internal {
+// the march on device arrays, for the session runtime (fdcn_session.hip)
+int launch_march(int it, int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
+                 const double* params, const int32_t* iparams, const double* v_init,
+                 const double* payoff, int32_t n_mon, const int32_t* mon_step,
+                 const double* mon_rebate, double* v_out, int32_t k_cap, double* workspace,
+                 int64_t workspace_bytes, hipStream_t stream) {
+  return launch(it, B, n_nodes, n_time, n_ranna, params, iparams, v_init, payoff, n_mon,
+                mon_step, mon_rebate, v_out, k_cap, workspace, workspace_bytes, stream);
+}
+
 // One non-blocking stream per (calling thread, device), created on first
 // use: host-array calls from different threads never share a stream or wait
 // for each other, and nothing is synchronised device-wide.  The device's
 // default memory pool keeps freed blocks (release threshold = max), so the
-// per-call stream-ordered allocations below are pool hits after warm-up.
+// per-call stream-ordered blocks (fdcn_host_call.h) are pool hits after warm-up.
 int thread_stream(hipStream_t* out) {
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
@@ -3145,95 +3195,6 @@ int thread_stream(hipStream_t* out) {
   *out = streams[dev];
   return FDCN_OK;
 }
-
-size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-
-int host_batch(int it, int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
-               const double* params, const int32_t* iparams, const double* v_init,
-               const double* payoff, int32_t n_mon, const int32_t* mon_step,
-               const double* mon_rebate, double* v_out) {
-  int rc = validate_plan(it, B, n_nodes, n_time, n_ranna, params, iparams, n_mon, mon_step,
-                         mon_rebate);
-  if (rc) return rc;
-  if (B > 0 && (!v_init || !v_out || (it && !payoff)))
-    return fail(FDCN_EINVAL, "null array argument");
-  if (B == 0) return FDCN_OK;
-  const int k_cap = fdcn_sm_extent(B, n_nodes, n_time, n_ranna, params);
-  if (k_cap < 0) return k_cap;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(FDCN_ENODEV, "no HIP device visible");
-  int32_t w_, npt_, spb_, lds_;
-  int64_t ws_ = 0;
-  rc = fdcn_plan(B, n_nodes, n_time, it, k_cap, &w_, &npt_, &spb_, &lds_, &ws_);
-  if (rc) return rc;
-  hipStream_t stream;
-  rc = thread_stream(&stream);
-  if (rc) return rc;
-
-  // one stream-ordered block for every device array of the call
-  const size_t nv = (size_t)B * n_nodes;
-  const size_t nm = (size_t)(n_mon > 0 ? n_mon : 1);
-  const size_t oP = 0;
-  const size_t oI = oP + align256(sizeof(double) * (size_t)B * FDCN_NPARAM);
-  const size_t oV = oI + align256(sizeof(int32_t) * (size_t)B * FDCN_NIPARAM);
-  const size_t oO = oV + align256(sizeof(double) * nv);
-  const size_t oF = oO + align256(sizeof(double) * nv);
-  const size_t oM = oF + (it ? align256(sizeof(double) * nv) : 0);
-  const size_t oR = oM + align256(sizeof(int32_t) * nm);
-  const size_t oW = oR + align256(sizeof(double) * nm);
-  const size_t ws_bytes = (size_t)ws_ * (size_t)B;
-  const size_t total = oW + align256(ws_bytes > 0 ? ws_bytes : 1);
-  char* blk = nullptr;
-  hipError_t e = hipMallocAsync((void**)&blk, total, stream);
-  if (e != hipSuccess)
-    return fail(FDCN_ENOMEM, "hipMallocAsync(%zu) failed: %s", total, hipGetErrorString(e));
-  double* dP = (double*)(blk + oP);
-  int32_t* dI = (int32_t*)(blk + oI);
-  double* dV = (double*)(blk + oV);
-  double* dO = (double*)(blk + oO);
-  double* dF = it ? (double*)(blk + oF) : nullptr;
-  int32_t* dM = (int32_t*)(blk + oM);
-  double* dR = (double*)(blk + oR);
-  double* dW = (double*)(blk + oW);
-  const hipMemcpyKind h2d = hipMemcpyHostToDevice;
-  e = hipMemcpyAsync(dP, params, sizeof(double) * (size_t)B * FDCN_NPARAM, h2d, stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(dI, iparams, sizeof(int32_t) * (size_t)B * FDCN_NIPARAM, h2d, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dV, v_init, sizeof(double) * nv, h2d, stream);
-  if (e == hipSuccess && it) e = hipMemcpyAsync(dF, payoff, sizeof(double) * nv, h2d, stream);
-  if (e == hipSuccess && n_mon > 0)
-    e = hipMemcpyAsync(dM, mon_step, sizeof(int32_t) * (size_t)n_mon, h2d, stream);
-  if (e == hipSuccess && n_mon > 0)
-    e = hipMemcpyAsync(dR, mon_rebate, sizeof(double) * (size_t)n_mon, h2d, stream);
-  if (e != hipSuccess) rc = fail(FDCN_EHIP, "hipMemcpyAsync H2D failed: %s", hipGetErrorString(e));
-  if (rc == FDCN_OK)
-    rc = launch(it, B, n_nodes, n_time, n_ranna, dP, dI, dV, dF, n_mon, dM, dR, dO, k_cap, dW,
-                (int64_t)ws_bytes, stream);
-  if (rc == FDCN_OK) {
-    e = hipMemcpyAsync(v_out, dO, sizeof(double) * nv, hipMemcpyDeviceToHost, stream);
-    if (e != hipSuccess) rc = fail(FDCN_EHIP, "hipMemcpyAsync D2H failed: %s", hipGetErrorString(e));
-  }
-  (void)hipFreeAsync(blk, stream);
-  e = hipStreamSynchronize(stream);
-  if (rc == FDCN_OK && e != hipSuccess)
-    rc = fail(FDCN_EHIP, "kernel / copies failed: %s", hipGetErrorString(e));
-  return rc;
-}
-
-}  // namespace
-
-namespace fdcn_internal {
-// the march, for the session runtime (fdcn_session.hip)
-int launch_march(int it, int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
-                 const double* params, const int32_t* iparams, const double* v_init,
-                 const double* payoff, int32_t n_mon, const int32_t* mon_step,
-                 const double* mon_rebate, double* v_out, int32_t k_cap, double* workspace,
-                 int64_t workspace_bytes, hipStream_t stream) {
-  return launch(it, B, n_nodes, n_time, n_ranna, params, iparams, v_init, payoff, n_mon,
-                mon_step, mon_rebate, v_out, k_cap, workspace, workspace_bytes, stream);
-}
-int thread_stream(hipStream_t* out) { return ::thread_stream(out); }
 }  // namespace fdcn_internal
 
 // ---------------------------------------------------------------------------

@@ -32,13 +32,9 @@
 #include "../../include/fdcn.h"
 #include "../../include/fdcn_diag.h"
 #include "fdcn_philox.h"
+#include "fdcn_shared.h"
 
 #pragma clang fp contract(off)
-
-namespace fdcn_internal {
-int set_error(int code, const char* msg);     // fdcn_kernels.hip (fdcn_last_error)
-int thread_stream(hipStream_t* out);          // fdcn_kernels.hip (one per thread, device)
-}
 
 namespace {
 
@@ -269,8 +265,6 @@ int launch(int32_t B, int32_t n_steps, int64_t n_obs, int32_t antithetic, const 
   return FDCN_OK;
 }
 
-size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-
 }  // namespace
 
 extern "C" {
@@ -297,25 +291,12 @@ int fdcn_mc_barrier_batch_dev(int32_t B, int32_t n_steps, int64_t n_obs, int32_t
   if (!flags) return mfail(FDCN_EINVAL, "mc_barrier_batch_dev: flags is NULL");
   if (!step) return mfail(FDCN_EINVAL, "mc_barrier_batch_dev: step is NULL");
   if (!stats) return mfail(FDCN_EINVAL, "mc_barrier_batch_dev: stats is NULL");
-  const int64_t need = blocks_for(n_obs) * 2 * (int64_t)sizeof(double) * B;
-  if (workspace && workspace_bytes < need) {
-    char msg[160];
-    snprintf(msg, sizeof msg,
-             "mc_barrier_batch_dev: workspace of %lld B is smaller than the %lld B this launch "
-             "needs (fdcn_mc_plan)", (long long)workspace_bytes, (long long)need);
-    return mfail(FDCN_EINVAL, msg);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  bool own = false;
-  if (!workspace) {  // stream-ordered scratch, released after the launch
-    if (hipMallocAsync((void**)&workspace, (size_t)need, s) != hipSuccess)
-      return mfail(FDCN_ENOMEM, "mc_barrier_batch_dev: hipMallocAsync failed");
-    own = true;
-  }
-  rc = launch(B, n_steps, n_obs, antithetic, params, flags, step, z, seed, obs_first, stats,
-              payoff_out, workspace, s);
-  if (own) (void)hipFreeAsync(workspace, s);
-  return rc;
+  return fdcn_call::with_workspace<fdcn_internal::HipCall>(
+      "mc_barrier_batch_dev", "this launch needs (fdcn_mc_plan)", workspace, workspace_bytes,
+      blocks_for(n_obs) * 2 * (int64_t)sizeof(double) * B, (hipStream_t)stream, [&](void* ws) {
+        return launch(B, n_steps, n_obs, antithetic, params, flags, step, z, seed, obs_first,
+                      stats, payoff_out, (double*)ws, (hipStream_t)stream);
+      });
 }
 
 int fdcn_mc_barrier_batch(int32_t B, int32_t n_steps, int64_t n_obs, int32_t antithetic,
@@ -330,54 +311,21 @@ int fdcn_mc_barrier_batch(int32_t B, int32_t n_steps, int64_t n_obs, int32_t ant
   if (!stats) return mfail(FDCN_EINVAL, "mc_barrier_batch: stats is NULL");
   rc = check_contracts(B, params, flags);
   if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return mfail(FDCN_ENODEV, "no HIP device visible");
-  hipStream_t stream;
-  rc = fdcn_internal::thread_stream(&stream);
-  if (rc) return rc;
-
-  // one stream-ordered block for every device array of the call
+  fdcn_internal::HostCall c("mc_barrier_batch");
+  if ((rc = c.open())) return rc;
   const size_t nb = (size_t)B;
-  const size_t bP = sizeof(double) * nb * FDCN_MC_NPARAM;
-  const size_t bF = sizeof(int32_t) * nb * FDCN_MC_NFLAG;
-  const size_t bS = sizeof(double) * nb * (size_t)n_steps * FDCN_MC_NSTEP;
-  const size_t bZ = z ? sizeof(double) * (size_t)n_obs * (size_t)n_steps : 0;
-  const size_t bO = sizeof(double) * nb * FDCN_MC_NSTAT;
-  const size_t bY = payoff_out ? sizeof(double) * nb * (size_t)n_obs : 0;
-  const size_t bW = sizeof(double) * 2 * (size_t)blocks_for(n_obs) * nb;
-  const size_t oP = 0;
-  const size_t oF = oP + align256(bP);
-  const size_t oS = oF + align256(bF);
-  const size_t oZ = oS + align256(bS);
-  const size_t oO = oZ + align256(bZ);
-  const size_t oY = oO + align256(bO);
-  const size_t oW = oY + align256(bY);
-  const size_t total = oW + align256(bW);
-  char* blk = nullptr;
-  if (hipMallocAsync((void**)&blk, total, stream) != hipSuccess)
-    return mfail(FDCN_ENOMEM, "mc_barrier_batch: hipMallocAsync failed");
-  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
-  hipError_t e = hipMemcpyAsync(blk + oP, params, bP, h2d, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(blk + oF, flags, bF, h2d, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(blk + oS, step, bS, h2d, stream);
-  if (e == hipSuccess && z) e = hipMemcpyAsync(blk + oZ, z, bZ, h2d, stream);
-  if (e != hipSuccess) rc = mfail(FDCN_EHIP, "mc_barrier_batch: H2D copy failed");
-  if (rc == FDCN_OK)
-    rc = launch(B, n_steps, n_obs, antithetic, (const double*)(blk + oP),
-                (const int32_t*)(blk + oF), (const double*)(blk + oS),
-                z ? (const double*)(blk + oZ) : nullptr, seed, obs_first, (double*)(blk + oO),
-                payoff_out ? (double*)(blk + oY) : nullptr, (double*)(blk + oW), stream);
-  if (rc == FDCN_OK) {
-    e = hipMemcpyAsync(stats, blk + oO, bO, d2h, stream);
-    if (e == hipSuccess && payoff_out) e = hipMemcpyAsync(payoff_out, blk + oY, bY, d2h, stream);
-    if (e != hipSuccess) rc = mfail(FDCN_EHIP, "mc_barrier_batch: D2H copy failed");
-  }
-  (void)hipFreeAsync(blk, stream);
-  e = hipStreamSynchronize(stream);
-  if (rc == FDCN_OK && e != hipSuccess)
-    rc = mfail(FDCN_EHIP, "mc_barrier_batch: kernel / copies failed");
-  return rc;
+  const int rP = c.in(params, sizeof(double) * nb * FDCN_MC_NPARAM);
+  const int rF = c.in(flags, sizeof(int32_t) * nb * FDCN_MC_NFLAG);
+  const int rS = c.in(step, sizeof(double) * nb * (size_t)n_steps * FDCN_MC_NSTEP);
+  const int rZ = c.in(z, sizeof(double) * (size_t)n_obs * (size_t)n_steps);
+  const int rO = c.out(stats, sizeof(double) * nb * FDCN_MC_NSTAT);
+  const int rY = c.out(payoff_out, sizeof(double) * nb * (size_t)n_obs);
+  const int rW = c.scratch(sizeof(double) * 2 * (size_t)blocks_for(n_obs) * nb);
+  return c.run([&](hipStream_t stream) {
+    return launch(B, n_steps, n_obs, antithetic, c.dev<double>(rP), c.dev<int32_t>(rF),
+                  c.dev<double>(rS), c.dev<double>(rZ), seed, obs_first, c.dev<double>(rO),
+                  c.dev<double>(rY), c.dev<double>(rW), stream);
+  });
 }
 
 int fdcn_mc_normals(int64_t n_obs, int32_t n_steps, uint64_t seed, int32_t stream_id,
@@ -390,25 +338,16 @@ int fdcn_mc_normals(int64_t n_obs, int32_t n_steps, uint64_t seed, int32_t strea
   const int64_t grid = (threads + kThreads - 1) / kThreads;
   if (n_obs > ((int64_t)1 << 40) || grid > 0x7fffffffLL)
     return mfail(FDCN_EINVAL, "mc_normals: n_obs * n_steps is beyond one launch's grid");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return mfail(FDCN_ENODEV, "no HIP device visible");
-  hipStream_t stream;
-  int rc = fdcn_internal::thread_stream(&stream);
+  fdcn_internal::HostCall c("mc_normals");
+  const int rc = c.open();
   if (rc) return rc;
-  const size_t bytes = sizeof(double) * (size_t)n_obs * (size_t)n_steps;
-  double* dz = nullptr;
-  if (hipMallocAsync((void**)&dz, bytes, stream) != hipSuccess)
-    return mfail(FDCN_ENOMEM, "mc_normals: hipMallocAsync failed");
-  hipLaunchKernelGGL(mc_normals_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, stream, n_obs,
-                     n_steps, seed, (uint32_t)stream_id, obs_first, dz);
-  if (hipGetLastError() != hipSuccess) rc = mfail(FDCN_EHIP, "mc_normals: launch failed");
-  if (rc == FDCN_OK && hipMemcpyAsync(z, dz, bytes, hipMemcpyDeviceToHost, stream) != hipSuccess)
-    rc = mfail(FDCN_EHIP, "mc_normals: D2H copy failed");
-  (void)hipFreeAsync(dz, stream);
-  const hipError_t e = hipStreamSynchronize(stream);
-  if (rc == FDCN_OK && e != hipSuccess) rc = mfail(FDCN_EHIP, "mc_normals: kernel / copy failed");
-  return rc;
+  const int rZ = c.out(z, sizeof(double) * (size_t)n_obs * (size_t)n_steps);
+  return c.run([&](hipStream_t stream) {
+    hipLaunchKernelGGL(mc_normals_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, stream, n_obs,
+                       n_steps, seed, (uint32_t)stream_id, obs_first, c.dev<double>(rZ));
+    return hipGetLastError() == hipSuccess ? FDCN_OK
+                                           : mfail(FDCN_EHIP, "mc_normals: launch failed");
+  });
 }
 
 }  // extern "C"

@@ -34,13 +34,9 @@
 
 #include "../../include/fdcn.h"
 #include "fdcn_philox.h"
+#include "fdcn_shared.h"
 
 #pragma clang fp contract(off)
-
-namespace fdcn_internal {
-int set_error(int code, const char* msg);     // fdcn_kernels.hip (fdcn_last_error)
-int thread_stream(hipStream_t* out);          // fdcn_kernels.hip (one per thread, device)
-}
 
 namespace {
 
@@ -349,8 +345,6 @@ int launch(int32_t B, int32_t G, int32_t n_steps, int64_t n_obs, int32_t antithe
   return FDCN_OK;
 }
 
-size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-
 }  // namespace
 
 extern "C" {
@@ -377,25 +371,12 @@ int fdcn_mc_bgk_batch_dev(int32_t B, int32_t G, int32_t n_steps, int64_t n_obs,
   if (!flags) return bfail(FDCN_EINVAL, "mc_bgk_batch_dev: flags is NULL");
   if (!step) return bfail(FDCN_EINVAL, "mc_bgk_batch_dev: step is NULL");
   if (!stats) return bfail(FDCN_EINVAL, "mc_bgk_batch_dev: stats is NULL");
-  const int64_t need = ws_bytes(B, G, n_obs);
-  if (workspace && workspace_bytes < need) {
-    char msg[160];
-    snprintf(msg, sizeof msg,
-             "mc_bgk_batch_dev: workspace of %lld B is smaller than the %lld B this launch "
-             "needs (fdcn_mc_bgk_plan)", (long long)workspace_bytes, (long long)need);
-    return bfail(FDCN_EINVAL, msg);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  bool own = false;
-  if (!workspace) {  // stream-ordered scratch, released after the launch
-    if (hipMallocAsync((void**)&workspace, (size_t)need, s) != hipSuccess)
-      return bfail(FDCN_ENOMEM, "mc_bgk_batch_dev: hipMallocAsync failed");
-    own = true;
-  }
-  rc = launch(B, G, n_steps, n_obs, antithetic, params, flags, step, z, seed, obs_first, stats,
-              payoff_out, workspace, s);
-  if (own) (void)hipFreeAsync(workspace, s);
-  return rc;
+  return fdcn_call::with_workspace<fdcn_internal::HipCall>(
+      "mc_bgk_batch_dev", "this launch needs (fdcn_mc_bgk_plan)", workspace, workspace_bytes,
+      ws_bytes(B, G, n_obs), (hipStream_t)stream, [&](void* ws) {
+        return launch(B, G, n_steps, n_obs, antithetic, params, flags, step, z, seed, obs_first,
+                      stats, payoff_out, (double*)ws, (hipStream_t)stream);
+      });
 }
 
 int fdcn_mc_bgk_batch(int32_t B, int32_t G, int32_t n_steps, int64_t n_obs, int32_t antithetic,
@@ -410,55 +391,22 @@ int fdcn_mc_bgk_batch(int32_t B, int32_t G, int32_t n_steps, int64_t n_obs, int3
   if (!stats) return bfail(FDCN_EINVAL, "mc_bgk_batch: stats is NULL");
   rc = check_trades(B, G, params, flags);
   if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return bfail(FDCN_ENODEV, "no HIP device visible");
-  hipStream_t stream;
-  rc = fdcn_internal::thread_stream(&stream);
-  if (rc) return rc;
-
-  // one stream-ordered block for every device array of the call
+  fdcn_internal::HostCall c("mc_bgk_batch");
+  if ((rc = c.open())) return rc;
   const size_t rows = (size_t)B * (size_t)G;
   const size_t n_sim = (size_t)n_obs * (antithetic ? 2 : 1);
-  const size_t bP = sizeof(double) * rows * FDCN_BGK_NPARAM;
-  const size_t bF = sizeof(int32_t) * (size_t)B * FDCN_BGK_NFLAG;
-  const size_t bS = sizeof(double) * rows * (size_t)n_steps * FDCN_BGK_NSTEP;
-  const size_t bZ = z ? sizeof(double) * (size_t)n_obs * (size_t)n_steps : 0;
-  const size_t bO = sizeof(double) * rows * FDCN_BGK_NSTAT;
-  const size_t bY = payoff_out ? sizeof(double) * rows * 2 * n_sim : 0;
-  const size_t bW = (size_t)ws_bytes(B, G, n_obs);
-  const size_t oP = 0;
-  const size_t oF = oP + align256(bP);
-  const size_t oS = oF + align256(bF);
-  const size_t oZ = oS + align256(bS);
-  const size_t oO = oZ + align256(bZ);
-  const size_t oY = oO + align256(bO);
-  const size_t oW = oY + align256(bY);
-  const size_t total = oW + align256(bW);
-  char* blk = nullptr;
-  if (hipMallocAsync((void**)&blk, total, stream) != hipSuccess)
-    return bfail(FDCN_ENOMEM, "mc_bgk_batch: hipMallocAsync failed");
-  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
-  hipError_t e = hipMemcpyAsync(blk + oP, params, bP, h2d, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(blk + oF, flags, bF, h2d, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(blk + oS, step, bS, h2d, stream);
-  if (e == hipSuccess && z) e = hipMemcpyAsync(blk + oZ, z, bZ, h2d, stream);
-  if (e != hipSuccess) rc = bfail(FDCN_EHIP, "mc_bgk_batch: H2D copy failed");
-  if (rc == FDCN_OK)
-    rc = launch(B, G, n_steps, n_obs, antithetic, (const double*)(blk + oP),
-                (const int32_t*)(blk + oF), (const double*)(blk + oS),
-                z ? (const double*)(blk + oZ) : nullptr, seed, obs_first, (double*)(blk + oO),
-                payoff_out ? (double*)(blk + oY) : nullptr, (double*)(blk + oW), stream);
-  if (rc == FDCN_OK) {
-    e = hipMemcpyAsync(stats, blk + oO, bO, d2h, stream);
-    if (e == hipSuccess && payoff_out) e = hipMemcpyAsync(payoff_out, blk + oY, bY, d2h, stream);
-    if (e != hipSuccess) rc = bfail(FDCN_EHIP, "mc_bgk_batch: D2H copy failed");
-  }
-  (void)hipFreeAsync(blk, stream);
-  e = hipStreamSynchronize(stream);
-  if (rc == FDCN_OK && e != hipSuccess)
-    rc = bfail(FDCN_EHIP, "mc_bgk_batch: kernel / copies failed");
-  return rc;
+  const int rP = c.in(params, sizeof(double) * rows * FDCN_BGK_NPARAM);
+  const int rF = c.in(flags, sizeof(int32_t) * (size_t)B * FDCN_BGK_NFLAG);
+  const int rS = c.in(step, sizeof(double) * rows * (size_t)n_steps * FDCN_BGK_NSTEP);
+  const int rZ = c.in(z, sizeof(double) * (size_t)n_obs * (size_t)n_steps);
+  const int rO = c.out(stats, sizeof(double) * rows * FDCN_BGK_NSTAT);
+  const int rY = c.out(payoff_out, sizeof(double) * rows * 2 * n_sim);
+  const int rW = c.scratch((size_t)ws_bytes(B, G, n_obs));
+  return c.run([&](hipStream_t stream) {
+    return launch(B, G, n_steps, n_obs, antithetic, c.dev<double>(rP), c.dev<int32_t>(rF),
+                  c.dev<double>(rS), c.dev<double>(rZ), seed, obs_first, c.dev<double>(rO),
+                  c.dev<double>(rY), c.dev<double>(rW), stream);
+  });
 }
 
 }  // extern "C"

@@ -31,13 +31,9 @@
 
 #include "../../include/fdcn.h"
 #include "fdcn_philox.h"
+#include "fdcn_shared.h"
 
 #pragma clang fp contract(off)
-
-namespace fdcn_internal {
-int set_error(int code, const char* msg);     // fdcn_kernels.hip (fdcn_last_error)
-int thread_stream(hipStream_t* out);          // fdcn_kernels.hip (one per thread, device)
-}
 
 namespace {
 
@@ -497,8 +493,6 @@ int launch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic, const doub
   return FDCN_OK;
 }
 
-size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-
 }  // namespace
 
 extern "C" {
@@ -524,25 +518,12 @@ int fdcn_mc_lsm_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithe
   if (rc) return rc;
   rc = check_pointers("mc_lsm_batch_dev", params, flags, step, stats);
   if (rc) return rc;
-  const int64_t need = ws_bytes(G) * B;
-  if (workspace && workspace_bytes < need) {
-    char msg[160];
-    snprintf(msg, sizeof msg,
-             "mc_lsm_batch_dev: workspace of %lld B is smaller than the %lld B this launch "
-             "needs (fdcn_mc_lsm_plan)", (long long)workspace_bytes, (long long)need);
-    return lfail(FDCN_EINVAL, msg);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  bool own = false;
-  if (!workspace) {  // stream-ordered scratch, released after the launch
-    if (hipMallocAsync((void**)&workspace, (size_t)need, s) != hipSuccess)
-      return lfail(FDCN_ENOMEM, "mc_lsm_batch_dev: hipMallocAsync failed");
-    own = true;
-  }
-  rc = launch(B, n_steps, G, antithetic, params, flags, step, seed, obs_first, stats, values_out,
-              coef_out, workspace, s);
-  if (own) (void)hipFreeAsync(workspace, s);
-  return rc;
+  return fdcn_call::with_workspace<fdcn_internal::HipCall>(
+      "mc_lsm_batch_dev", "this launch needs (fdcn_mc_lsm_plan)", workspace, workspace_bytes,
+      ws_bytes(G) * B, (hipStream_t)stream, [&](void* ws) {
+        return launch(B, n_steps, G, antithetic, params, flags, step, seed, obs_first, stats,
+                      values_out, coef_out, (double*)ws, (hipStream_t)stream);
+      });
 }
 
 int fdcn_mc_lsm_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
@@ -555,54 +536,21 @@ int fdcn_mc_lsm_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
   if (rc) return rc;
   rc = check_contracts(B, n_steps, params, flags, step);
   if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return lfail(FDCN_ENODEV, "no HIP device visible");
-  hipStream_t stream;
-  rc = fdcn_internal::thread_stream(&stream);
-  if (rc) return rc;
-
-  // one stream-ordered block for every device array of the call
+  fdcn_internal::HostCall c("mc_lsm_batch");
+  if ((rc = c.open())) return rc;
   const size_t nb = (size_t)B;
-  const size_t bP = sizeof(double) * nb * FDCN_LSM_NPARAM;
-  const size_t bF = sizeof(int32_t) * nb * FDCN_LSM_NFLAG;
-  const size_t bS = sizeof(double) * nb * (size_t)n_steps * FDCN_LSM_NSTEP;
-  const size_t bO = sizeof(double) * nb * FDCN_LSM_NSTAT;
-  const size_t bY = values_out ? sizeof(double) * nb * (size_t)G * kSubrun : 0;
-  const size_t bC = coef_out ? sizeof(double) * nb * (size_t)G * n_steps * FDCN_LSM_NCOEF : 0;
-  const size_t bW = (size_t)ws_bytes(G) * nb;
-  const size_t oP = 0;
-  const size_t oF = oP + align256(bP);
-  const size_t oS = oF + align256(bF);
-  const size_t oO = oS + align256(bS);
-  const size_t oY = oO + align256(bO);
-  const size_t oC = oY + align256(bY);
-  const size_t oW = oC + align256(bC);
-  const size_t total = oW + align256(bW);
-  char* blk = nullptr;
-  if (hipMallocAsync((void**)&blk, total, stream) != hipSuccess)
-    return lfail(FDCN_ENOMEM, "mc_lsm_batch: hipMallocAsync failed");
-  const hipMemcpyKind h2d = hipMemcpyHostToDevice, d2h = hipMemcpyDeviceToHost;
-  hipError_t e = hipMemcpyAsync(blk + oP, params, bP, h2d, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(blk + oF, flags, bF, h2d, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(blk + oS, step, bS, h2d, stream);
-  if (e != hipSuccess) rc = lfail(FDCN_EHIP, "mc_lsm_batch: H2D copy failed");
-  if (rc == FDCN_OK)
-    rc = launch(B, n_steps, G, antithetic, (const double*)(blk + oP), (const int32_t*)(blk + oF),
-                (const double*)(blk + oS), seed, obs_first, (double*)(blk + oO),
-                values_out ? (double*)(blk + oY) : nullptr,
-                coef_out ? (double*)(blk + oC) : nullptr, (double*)(blk + oW), stream);
-  if (rc == FDCN_OK) {
-    e = hipMemcpyAsync(stats, blk + oO, bO, d2h, stream);
-    if (e == hipSuccess && values_out) e = hipMemcpyAsync(values_out, blk + oY, bY, d2h, stream);
-    if (e == hipSuccess && coef_out) e = hipMemcpyAsync(coef_out, blk + oC, bC, d2h, stream);
-    if (e != hipSuccess) rc = lfail(FDCN_EHIP, "mc_lsm_batch: D2H copy failed");
-  }
-  (void)hipFreeAsync(blk, stream);
-  e = hipStreamSynchronize(stream);
-  if (rc == FDCN_OK && e != hipSuccess)
-    rc = lfail(FDCN_EHIP, "mc_lsm_batch: kernel / copies failed");
-  return rc;
+  const int rP = c.in(params, sizeof(double) * nb * FDCN_LSM_NPARAM);
+  const int rF = c.in(flags, sizeof(int32_t) * nb * FDCN_LSM_NFLAG);
+  const int rS = c.in(step, sizeof(double) * nb * (size_t)n_steps * FDCN_LSM_NSTEP);
+  const int rO = c.out(stats, sizeof(double) * nb * FDCN_LSM_NSTAT);
+  const int rY = c.out(values_out, sizeof(double) * nb * (size_t)G * kSubrun);
+  const int rC = c.out(coef_out, sizeof(double) * nb * (size_t)G * n_steps * FDCN_LSM_NCOEF);
+  const int rW = c.scratch((size_t)ws_bytes(G) * nb);
+  return c.run([&](hipStream_t stream) {
+    return launch(B, n_steps, G, antithetic, c.dev<double>(rP), c.dev<int32_t>(rF),
+                  c.dev<double>(rS), seed, obs_first, c.dev<double>(rO), c.dev<double>(rY),
+                  c.dev<double>(rC), c.dev<double>(rW), stream);
+  });
 }
 
 }  // extern "C"

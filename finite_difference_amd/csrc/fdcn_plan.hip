@@ -23,10 +23,7 @@
 #include <vector>
 
 #include "../../include/fdcn.h"
-
-namespace fdcn_internal {
-int set_error(int code, const char* msg);
-}
+#include "fdcn_shared.h"
 
 namespace {
 

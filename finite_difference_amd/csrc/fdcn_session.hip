@@ -43,18 +43,7 @@
 
 #include "../../include/fdcn.h"
 #include "fdcn_session_book.h"
-
-namespace fdcn_internal {
-int set_error(int code, const char* msg);
-int validate_plan(int it, int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
-                  const double* params, const int32_t* iparams, int32_t n_mon,
-                  const int32_t* mon_step, const double* mon_rebate);
-int launch_march(int it, int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
-                 const double* params, const int32_t* iparams, const double* v_init,
-                 const double* payoff, int32_t n_mon, const int32_t* mon_step,
-                 const double* mon_rebate, double* v_out, int32_t k_cap, double* workspace,
-                 int64_t workspace_bytes, hipStream_t stream);
-}  // namespace fdcn_internal
+#include "fdcn_shared.h"
 
 namespace {
 

@@ -1,12 +1,16 @@
 // fdcn_shared.h -- internal to libfdcn: the helpers the device march and
-// the host-only translation unit (fdcn_host.hip) both evaluate, and the
-// host-side checks the launch paths share.  Not part of the C ABI.
+// the host-only translation unit (fdcn_host.hip) both evaluate, the
+// host-side checks the launch paths share, what one unit calls of another,
+// and the HIP backend of the host-array staging (fdcn_host_call.h).  Not part
+// of the C ABI.
 #ifndef FDCN_SHARED_H
 #define FDCN_SHARED_H
 
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include "fdcn_host_call.h"
 
 namespace fdcn_internal {
 
@@ -84,6 +88,38 @@ int validate_common(int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna)
 int validate_plan(int it, int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
                   const double* params, const int32_t* iparams, int32_t n_mon,
                   const int32_t* mon_step, const double* mon_rebate);
+// the calling thread's non-blocking stream on the current device (fdcn_kernels.hip)
+int thread_stream(hipStream_t* out);
+// the march on device arrays, for the session runtime (fdcn_kernels.hip)
+int launch_march(int it, int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
+                 const double* params, const int32_t* iparams, const double* v_init,
+                 const double* payoff, int32_t n_mon, const int32_t* mon_step,
+                 const double* mon_rebate, double* v_out, int32_t k_cap, double* workspace,
+                 int64_t workspace_bytes, hipStream_t stream);
+
+// The HIP backend of fdcn_host_call.h: stream-ordered allocation from the
+// device pool and asynchronous copies on the calling thread's stream.
+struct HipCall {
+  using Stream = hipStream_t;
+  static int open(hipStream_t* s) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+      return set_error(FDCN_ENODEV, "no HIP device visible");
+    return thread_stream(s);
+  }
+  static const char* text(hipError_t e) { return e == hipSuccess ? nullptr : hipGetErrorString(e); }
+  static const char* alloc(void** p, size_t n, hipStream_t s) { return text(hipMallocAsync(p, n, s)); }
+  static const char* release(void* p, hipStream_t s) { return text(hipFreeAsync(p, s)); }
+  static const char* copy_in(void* dev, const void* host, size_t n, hipStream_t s) {
+    return text(hipMemcpyAsync(dev, host, n, hipMemcpyHostToDevice, s));
+  }
+  static const char* copy_out(void* host, const void* dev, size_t n, hipStream_t s) {
+    return text(hipMemcpyAsync(host, dev, n, hipMemcpyDeviceToHost, s));
+  }
+  static const char* sync(hipStream_t s) { return text(hipStreamSynchronize(s)); }
+  static int fail(int code, const char* msg) { return set_error(code, msg); }
+};
+using HostCall = fdcn_call::HostCall<HipCall>;
 
 }  // namespace fdcn_internal
 

@@ -40,14 +40,7 @@
 #include <type_traits>
 
 #include "../../include/fdcn.h"
-
-namespace fdcn_internal {
-int set_error(int code, const char* msg);
-int validate_plan(int it, int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
-                  const double* params, const int32_t* iparams, int32_t n_mon,
-                  const int32_t* mon_step, const double* mon_rebate);
-int thread_stream(hipStream_t* out);
-}  // namespace fdcn_internal
+#include "fdcn_shared.h"
 
 namespace {
 
@@ -975,15 +968,6 @@ int vc_launch(int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna, const
   if (B == 0) return FDCN_OK;
   const VcVariant* v = vc_choose(n_nodes, B);
   if (!v) return vfail(FDCN_EINVAL, "fdcn_vc: n_nodes=%d above the largest variant", n_nodes);
-  const size_t ws = vc_ws_per_scen(*v) * (size_t)B;
-  if (workspace && (workspace_bytes < 0 || (size_t)workspace_bytes < ws))
-    return vfail(FDCN_EINVAL, "fdcn_vc: workspace of %lld B is smaller than the %zu B needed",
-                 (long long)workspace_bytes, ws);
-  bool own = false;
-  if (!workspace) {
-    V_TRY(hipMallocAsync((void**)&workspace, ws, stream));
-    own = true;
-  }
   VcArgs a;
   a.B = B;
   a.n = n_nodes;
@@ -999,22 +983,23 @@ int vc_launch(int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna, const
   a.mon_step = mon_step;
   a.mon_rebate = mon_rebate;
   a.v_out = v_out;
-  a.coef = workspace;
   (void)n_mon;
-  // classify + factor (one wave per scenario and phase), then both forms:
-  // each runs the scenarios the factor kernel gave it and returns at once
-  // for the others
-  hipLaunchKernelGGL(fdcn_vc_factor, dim3(B), dim3(128), 0, stream, a);
-  V_TRY(hipGetLastError());
-  hipLaunchKernelGGL(v->pointwise, dim3(B), dim3(64 * v->w), 0, stream, a);
-  V_TRY(hipGetLastError());
-  hipLaunchKernelGGL(v->stencil, dim3(B), dim3(64 * v->w), 0, stream, a);
-  V_TRY(hipGetLastError());
-  if (own) V_TRY(hipFreeAsync(workspace, stream));
-  return FDCN_OK;
+  return fdcn_call::with_workspace<fdcn_internal::HipCall>(
+      "fdcn_vc", "needed", workspace, workspace_bytes,
+      (int64_t)(vc_ws_per_scen(*v) * (size_t)B), stream, [&](void* ws) {
+        a.coef = (double*)ws;
+        // classify + factor (one wave per scenario and phase), then both
+        // forms: each runs the scenarios the factor kernel gave it and
+        // returns at once for the others
+        hipLaunchKernelGGL(fdcn_vc_factor, dim3(B), dim3(128), 0, stream, a);
+        V_TRY(hipGetLastError());
+        hipLaunchKernelGGL(v->pointwise, dim3(B), dim3(64 * v->w), 0, stream, a);
+        V_TRY(hipGetLastError());
+        hipLaunchKernelGGL(v->stencil, dim3(B), dim3(64 * v->w), 0, stream, a);
+        V_TRY(hipGetLastError());
+        return FDCN_OK;
+      });
 }
-
-size_t al256(size_t n) { return (n + 255) / 256 * 256; }
 
 }  // namespace
 
@@ -1104,45 +1089,27 @@ int fdcn_vc_batch(int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
     }
   }
   if (B == 0) return FDCN_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return vfail(FDCN_ENODEV, "no HIP device visible");
-  hipStream_t st;
-  int rc = fdcn_internal::thread_stream(&st);
+  fdcn_internal::HostCall c("fdcn_vc_batch");
+  int rc = c.open();
   if (rc) return rc;
   int32_t w_, npt_;
   int64_t wsp = 0;
   if ((rc = fdcn_vc_plan(B, n_nodes, &w_, &npt_, &wsp))) return rc;
-  const size_t nv = (size_t)B * n_nodes, nd = (size_t)B * 2 * FDCN_VC_NDIAG * n_nodes;
-  const size_t nb = (size_t)B * 2 * (size_t)n_time, nm = (size_t)(n_mon > 0 ? n_mon : 1);
-  const size_t oD = 0, oB = oD + al256(8 * nd), oV = oB + al256(8 * (nb ? nb : 1));
-  const size_t oI = oV + al256(8 * nv), oM = oI + al256(4 * (size_t)B * FDCN_NIPARAM);
-  const size_t oR = oM + al256(4 * nm), oO = oR + al256(8 * nm), oW = oO + al256(8 * nv);
-  const size_t ws = (size_t)wsp * B, total = oW + al256(ws);
-  char* d = nullptr;
-  hipError_t e = hipMallocAsync((void**)&d, total, st);
-  if (e != hipSuccess) return vfail(FDCN_ENOMEM, "hipMallocAsync(%zu): %s", total, hipGetErrorString(e));
-  const hipMemcpyKind h2d = hipMemcpyHostToDevice;
-  e = hipMemcpyAsync(d + oD, diag, 8 * nd, h2d, st);
-  if (e == hipSuccess && nb) e = hipMemcpyAsync(d + oB, bnd, 8 * nb, h2d, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + oV, v_init, 8 * nv, h2d, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d + oI, iparams, 4 * (size_t)B * FDCN_NIPARAM, h2d, st);
-  if (e == hipSuccess && n_mon > 0) e = hipMemcpyAsync(d + oM, mon_step, 4 * (size_t)n_mon, h2d, st);
-  if (e == hipSuccess && n_mon > 0) e = hipMemcpyAsync(d + oR, mon_rebate, 8 * (size_t)n_mon, h2d, st);
-  if (e != hipSuccess) rc = vfail(FDCN_EHIP, "hipMemcpyAsync H2D: %s", hipGetErrorString(e));
-  if (rc == FDCN_OK)
-    rc = vc_launch(B, n_nodes, n_time, n_ranna, (const double*)(d + oD), (const double*)(d + oB),
-                   (const double*)(d + oV), (const int32_t*)(d + oI), n_mon,
-                   (const int32_t*)(d + oM), (const double*)(d + oR), (double*)(d + oO),
-                   (double*)(d + oW), (int64_t)ws, st);
-  if (rc == FDCN_OK) {
-    e = hipMemcpyAsync(v_out, d + oO, 8 * nv, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) rc = vfail(FDCN_EHIP, "hipMemcpyAsync D2H: %s", hipGetErrorString(e));
-  }
-  (void)hipFreeAsync(d, st);
-  e = hipStreamSynchronize(st);
-  if (rc == FDCN_OK && e != hipSuccess) rc = vfail(FDCN_EHIP, "fdcn_vc: %s", hipGetErrorString(e));
-  return rc;
+  const size_t nv = 8 * (size_t)B * n_nodes, nb = 8 * (size_t)B * 2 * (size_t)n_time;
+  const size_t nm = (size_t)(n_mon > 0 ? n_mon : 1), ws = (size_t)wsp * B;
+  const int rD = c.in(diag, nv * 2 * FDCN_VC_NDIAG);
+  const int rB = c.in(bnd, nb, nb ? nb : 8);  // n_time = 0: one unread entry
+  const int rV = c.in(v_init, nv);
+  const int rI = c.in(iparams, 4 * (size_t)B * FDCN_NIPARAM);
+  const int rM = c.in(mon_step, 4 * (size_t)n_mon, 4 * nm);
+  const int rR = c.in(mon_rebate, 8 * (size_t)n_mon, 8 * nm);
+  const int rO = c.out(v_out, nv);
+  const int rW = c.scratch(ws);
+  return c.run([&](hipStream_t st) {
+    return vc_launch(B, n_nodes, n_time, n_ranna, c.dev<double>(rD), c.dev<double>(rB),
+                     c.dev<double>(rV), c.dev<int32_t>(rI), n_mon, c.dev<int32_t>(rM),
+                     c.dev<double>(rR), c.dev<double>(rO), c.dev<double>(rW), (int64_t)ws, st);
+  });
 }
 
 }  // extern "C"
