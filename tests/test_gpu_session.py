@@ -8,8 +8,9 @@
 * the device Greeks epilogue equals the host epilogue of the facades on the
   same GPU value vectors: bitwise for the barrier (…pricer.py:883-904) and
   CN-log (_cn.py:429-466) kinds, whose formulas are plain arithmetic in the
-  reference's order; to 1e-9 relative (Delta/Gamma 1e-7) for the American
-  kind, whose 4x4 cubic fit is a different LU than numpy's LAPACK;
+  reference's order; to 1e-12 relative (Delta/Gamma/theta 1.6e-12, eight
+  times the measured worst) for the American kind, whose 4x4 cubic fit is a
+  different LU than numpy's LAPACK;
 * the American trades with one and two discrete dividends (device jumps)
   match the reference's golden numbers (tolerances of test_gpu_pricers).
 """
@@ -157,8 +158,18 @@ def test_cn_log_device_epilogue_is_bitwise_host():
         assert dev.greeks() == host.greeks()
 
 
+AMERICAN_FIT_TOL = 8 * 1.94e-13
+
+
 @pytest.mark.parametrize("which", ["american", "black76"])
 def test_american_device_epilogue_matches_host(which):
+    """The kernel's cubic fit is its own LU, numpy's is LAPACK's: not the
+    same bits, but two orderings of one 4x4 solve.  Measured on the MI355X
+    over these eight contracts, |device - host| / max(1, |host|) is at most
+    2.2e-15 for Delta, 3.3e-15 for Gamma and 1.94e-13 for theta (price and
+    vega: 0); AMERICAN_FIT_TOL is that worst figure times the factor 8 of
+    the rounding yardsticks (it was 1e-7).  test_gpu_session_epilogue.py
+    holds the kernel's fit to the exact solve, case by case."""
     if which == "american":
         import test_american_host as T
     else:
@@ -171,7 +182,8 @@ def test_american_device_epilogue_matches_host(which):
         assert abs(gd["price"] - gh["price"]) <= 1e-12 * max(1.0, abs(gh["price"]))
         assert abs(gd["vega"] - gh["vega"]) <= 1e-12 * max(1.0, abs(gh["vega"]))
         for k in ("delta", "gamma", "theta"):
-            assert abs(gd[k] - gh[k]) <= 1e-7 * max(1.0, abs(gh[k])), (case["name"], k, gd, gh)
+            assert abs(gd[k] - gh[k]) <= AMERICAN_FIT_TOL * max(1.0, abs(gh[k])), (
+                case["name"], k, gd, gh)
 
 
 def test_american_dividend_trades_on_device_match_reference():
