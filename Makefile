@@ -17,8 +17,9 @@
 #                   the bitwise plan tests then run against it
 #                   then tools/sanitize/session_book_driver.cpp: the device
 #                   sessions' host-only bookkeeping (csrc/fdcn_session_book.h:
-#                   pinned staging arena, slot and event tables) under the same
-#                   two sanitizers, malloc standing in for hipHostMalloc
+#                   pinned staging arena, slot, event and exercise-region
+#                   tables) under the same two sanitizers, malloc standing in
+#                   for hipHostMalloc
 #   make tsan       the same two units under ThreadSanitizer with
 #                   tools/sanitize/plan_driver.cpp: the plan builders' worker
 #                   threads, two callers at once

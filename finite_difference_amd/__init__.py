@@ -14,6 +14,7 @@ from .mc_barrier import (NacaCurve, BarrierSpec, RebateSpec, MCConfig,  # noqa: 
 from .bgk_barrier import DiscreteBarrierBGKPricer, bgk_price_batch  # noqa: F401
 from .american_barrier import AmericanBarrierFDMPricer  # noqa: F401
 from .american_knockin import AmericanKnockInFDMPricer  # noqa: F401
+from .bermudan import BermudanFDMPricer  # noqa: F401
 from .mc_american import (LsmContract, LsmConfig, plan_american_contract,  # noqa: F401
                           contract_from_pricer, simulate_lsm, price_american_mc,
                           mc_american_batch, merge_lsm_stats)

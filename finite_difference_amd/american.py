@@ -24,9 +24,10 @@ tests) the host-side jump and epilogue below are used.
 
 What happens between two segments is an ordered list of events per grid job
 (``_job_events``): the dividend jump here, the knock-out of a monitoring
-date in american_barrier.py's subclass, and the knock-in of american_knockin.py,
-whose jobs march two coupled chains; vanilla and barrier trades march together
-in ``greeks_many`` / ``prefetch_many``.
+date in american_barrier.py's subclass, the knock-in of american_knockin.py,
+whose jobs march two coupled chains, and the exercise event of bermudan.py,
+whose segments are plain Crank-Nicolson; vanilla, barrier and Bermudan trades
+march together in ``greeks_many`` / ``prefetch_many``.
 """
 from __future__ import annotations
 
@@ -413,7 +414,9 @@ class AmericanFDMPricer:
         events[i] is the ordered list of maps applied to the value vector
         between segment i and segment i + 1 -- ("div", cash) for a dividend
         jump, ("ko", ko_lo, ko_hi, rebate) for a knock-out, ("ki", ko_lo,
-        ko_hi) for a knock-in from the coupled chain (subclasses) --
+        ko_hi) for a knock-in from the coupled chain, ("ex", ko_lo, ko_hi,
+        rebate) for a Bermudan exercise date and ("kop", ko_lo, ko_hi, rebate)
+        for a knock-out without an exercise floor (subclasses) --
         and restart[i] says whether segment i restarts the Rannacher steps
         (the reference: the first segment, and every segment of a call,
         fd_american_equity.py:825-843)."""
@@ -611,10 +614,12 @@ class AmericanFDMPricer:
         """_march_jobs with the value vectors in HBM: segment i of every job in
         lock-step launches (initial vectors: the payoff, then the previous
         segment's slots), the events between segments on the device (the
-        spline jumps into new slots, the knock-outs and knock-ins in place).
-        A job of more than one segment uploads its payoff once: its IT marches
-        and knock-outs name that slot.  Leaves each job's final slot in
-        job["slot"] (a knock-in job's coupled chain: job["wslot"])."""
+        spline jumps into new slots, the knock-outs, knock-ins and exercise
+        events in place).  A job of more than one segment uploads its payoff
+        once: its IT marches, knock-outs and exercise events name that slot.
+        Leaves each job's final slot in job["slot"] (a knock-in job's coupled
+        chain: job["wslot"]) and the ids of a Bermudan job's exercise regions
+        in job["region_ids"]."""
         n_seg = max(len(j["steps"]) for j in jobs)
         slot_of = {"v": "slot", "w": "wslot"}  # chain key -> where its slot is kept
         by_n: Dict[int, list] = {}
@@ -682,6 +687,19 @@ class AmericanFDMPricer:
                         sess.knockout([j["slot"] for j in js], n, [e[1] for e in ev],
                                       [e[2] for e in ev], [e[3] for e in ev],
                                       [j["pay"] for j in js])
+                        continue
+                    if kind == "kop":  # the plain projection: nobody may exercise there
+                        sess.knockout([j["slot"] for j in js], n, [e[1] for e in ev],
+                                      [e[2] for e in ev], [e[3] for e in ev], None)
+                        continue
+                    if kind == "ex":  # V <- max(V, payoff), the knocked nodes as "ko"
+                        bar = any(e[1] >= 0 or e[2] < n for e in ev)
+                        ids = sess.exercise([j["slot"] for j in js], n, [j["pay"] for j in js],
+                                            [e[1] for e in ev] if bar else None,
+                                            [e[2] for e in ev] if bar else None,
+                                            [e[3] for e in ev] if bar else None)
+                        for j, i in zip(js, ids):
+                            j["region_ids"].append(int(i))
                         continue
                     if kind == "ki":  # U <- W on the knocked nodes; W's slot is only read
                         sess.knockin([j["slot"] for j in js], n, [e[1] for e in ev],
@@ -854,8 +872,8 @@ class AmericanFDMPricer:
 
 def _job_slot_bytes(job: dict) -> int:
     """Bytes of the slots one job's chains create: one vector per march, one
-    per dividend jump (knock-outs and knock-ins run in place) and the uploaded
-    payoff; both chains of a knock-in job count.  It
+    per dividend jump (knock-outs, knock-ins and Bermudan exercise events run
+    in place) and the uploaded payoff; both chains of a knock-in job count.  It
     counts slots, not device memory: the block of every march also holds its
     copy of the initial vectors, the kernel workspace and, where the payoff
     slots are not consecutive, the gathered payoff, all kept until the session
@@ -882,8 +900,9 @@ def greeks_many(pricers: Sequence[AmericanFDMPricer], dv_sigma: float = 0.01,
     lock-step, with the spline jumps and the knock-outs on the device) march
     in shared launches, and the readouts, Richardson extrapolations, vega and
     theta run on the device (FDCN_GK_AMERICAN); six numbers per trade come
-    back.  Results land in each pricer's cache.  Vanilla, knock-out and
-    knock-in pricers (american_barrier.py, american_knockin.py) mix freely.
+    back.  Results land in each pricer's cache.  Vanilla, knock-out, knock-in
+    and Bermudan pricers (american_barrier.py, american_knockin.py,
+    bermudan.py) mix freely.
 
     Every march creates slots, so the slots of a chain take about n_segments x
     n_nodes x 8 bytes per grid until its session ends: when that estimate for

@@ -42,6 +42,7 @@ EXPORTED = ("fdcn_cn_batch", "fdcn_it_batch", "fdcn_cn_batch_dev", "fdcn_it_batc
             "fdcn_session_destroy", "fdcn_session_slots", "fdcn_session_host_buffer",
             "fdcn_session_march", "fdcn_session_march_ps", "fdcn_session_upload",
             "fdcn_session_knockout", "fdcn_session_knockin",
+            "fdcn_session_exercise", "fdcn_session_exercise_regions",
             "fdcn_session_dividend_jump", "fdcn_session_greeks", "fdcn_session_fetch",
             "fdcn_vc_batch", "fdcn_vc_batch_dev", "fdcn_vc_plan", "fdcn_barrier_plan",
             "fdcn_vmath", "fdcn_american_plan", "fdcn_device_ordinals",

@@ -18,7 +18,11 @@
 //   fdcn_session_knockout       monitoring-date knock-out of slots, in place
 //   fdcn_session_knockin        monitoring-date knock-in: masked copy from other
 //                               slots (the coupled American chain), in place
-//   fdcn_session_greeks         per-trade readouts + combinations -> T x 6
+//   fdcn_session_exercise       exercise date of a Bermudan chain: max(V, floor)
+//                               fused with the knock-out, in place; records
+//                               the exercise region of each vector
+//   fdcn_session_exercise_regions  those records back to the host
+//   fdcn_session_greeks        per-trade readouts + combinations -> T x 6
 //                               scalars back to the host
 //   fdcn_session_fetch          whole vectors back (when a caller wants them)
 //
@@ -134,6 +138,72 @@ knockin_kernel(int n, int chunks, const uint64_t* __restrict__ dst,
   const int j = (blockIdx.x % chunks) * 256 + threadIdx.x;
   if (j >= n || (j > ko_lo[b] && j < ko_hi[b])) return;
   reinterpret_cast<uint64_t*>(dst[b])[j] = reinterpret_cast<const uint64_t*>(src[b])[j];
+}
+
+// Exercise event of a Bermudan march, fused with the knock-out of a date that
+// is also monitored: on the knocked nodes (j <= ko_lo or j >= ko_hi; none when
+// ko_lo == NULL) of vector b, V_j <- max(floor_j, R_b); on every other node
+// V_j <- max(V_j, floor_j).  Both max pass a NaN of either operand on and keep
+// the first operand on ties, as np.maximum(floor, R) and np.maximum(V, floor).
+// One workgroup of 256 threads per vector strides along the nodes (contiguous
+// 8-byte accesses; a node is stored only where its value changes).  Each
+// thread keeps (min j, max j, count) of its nodes that are not knocked and
+// have floor_j > V_j (a NaN compares false): the exercise region.  The three
+// are reduced by shuffles within each wave of 64 and across the four waves
+// through LDS, and thread 0 stores them to region[b][0..2]: no atomics, so
+// the record does not depend on timing.  Empty region: (n, -1, 0).
+__global__ void __launch_bounds__(256)
+exercise_kernel(int n, const uint64_t* __restrict__ dst, const uint64_t* __restrict__ floor_src,
+                const int32_t* __restrict__ ko_lo, const int32_t* __restrict__ ko_hi,
+                const double* __restrict__ rebate, int32_t* __restrict__ region) {
+  __shared__ int32_t part[4][3];
+  const int b = blockIdx.x;
+  double* v = reinterpret_cast<double*>(dst[b]);
+  const double* f = reinterpret_cast<const double*>(floor_src[b]);
+  int lo = -1, hi = n;
+  double R = 0.0;
+  if (ko_lo) {
+    lo = ko_lo[b];
+    hi = ko_hi[b];
+    R = rebate[b];
+  }
+  int mn = n, mx = -1, cnt = 0;
+  for (int j = threadIdx.x; j < n; j += 256) {
+    const double fj = f[j];
+    if (j <= lo || j >= hi) {
+      v[j] = (fj >= R || fj != fj) ? fj : R;
+      continue;
+    }
+    const double vj = v[j];
+    if (fj > vj) {
+      mn = min(mn, j);
+      mx = j;  // j grows along the stride
+      ++cnt;
+    }
+    if (!(vj >= fj || vj != vj)) v[j] = fj;
+  }
+  for (int d = 32; d >= 1; d >>= 1) {
+    mn = min(mn, __shfl_down(mn, (unsigned)d, 64));
+    mx = max(mx, __shfl_down(mx, (unsigned)d, 64));
+    cnt += __shfl_down(cnt, (unsigned)d, 64);
+  }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    part[w][0] = mn;
+    part[w][1] = mx;
+    part[w][2] = cnt;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < 4; ++k) {
+      mn = min(mn, part[k][0]);
+      mx = max(mx, part[k][1]);
+      cnt += part[k][2];
+    }
+    region[3 * b + 0] = mn;
+    region[3 * b + 1] = mx;
+    region[3 * b + 2] = cnt;
+  }
 }
 
 // Dividend jump of one value vector per workgroup (fd_american_equity.py
@@ -398,6 +468,7 @@ struct fdcn_session {
   int rr = 0;
   std::vector<hipEvent_t> events;
   fdcn_book::SlotTable slots;
+  fdcn_book::RegionTable regions;
   struct Block {
     void* p;
     hipStream_t s;
@@ -832,6 +903,105 @@ int fdcn_session_knockin(fdcn_session* s, int32_t B, int32_t n_nodes, const int3
   int32_t ev;
   if ((rc = record(s, st, &ev))) return rc;
   for (int32_t b = 0; b < B; ++b) s->slots.ev[(size_t)slots[b]] = ev;  // consumers wait for it
+  return FDCN_OK;
+}
+
+int fdcn_session_exercise(fdcn_session* s, int32_t B, int32_t n_nodes, const int32_t* slots,
+                          const int32_t* floor_slots, const int32_t* ko_lo, const int32_t* ko_hi,
+                          const double* rebate, int32_t* out_region_ids) {
+  if (B < 1 || n_nodes < 1) return sfail(FDCN_EINVAL, "exercise: B >= 1, n_nodes >= 1");
+  if (!slots || !floor_slots || !out_region_ids)
+    return sfail(FDCN_EINVAL, "exercise: NULL argument (slots, floor_slots, out_region_ids)");
+  const bool barrier = ko_lo || ko_hi || rebate;
+  if (barrier && !(ko_lo && ko_hi && rebate))
+    return sfail(FDCN_EINVAL, "exercise: ko_lo, ko_hi and rebate go together (all or none)");
+  if (!s) return sfail(FDCN_EINVAL, "NULL session");
+  int rc = check_slots(s, B, slots, n_nodes);
+  if (rc) return rc;
+  if ((rc = check_slots(s, B, floor_slots, n_nodes))) return rc;
+  // as the knock-out: in place, so a slot named twice, or read as a floor
+  // while another vector's event writes it, would depend on timing
+  std::vector<int32_t> sorted(slots, slots + B);
+  std::sort(sorted.begin(), sorted.end());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+    return sfail(FDCN_EINVAL, "exercise: a slot appears twice in slots");
+  for (int32_t b = 0; b < B; ++b)
+    if (std::binary_search(sorted.begin(), sorted.end(), floor_slots[b]))
+      return sfail(FDCN_EINVAL, "exercise: floor slot %d is one of slots", floor_slots[b]);
+  Layout L;
+  const size_t oA = L.add(sizeof(uint64_t) * B);
+  const size_t oF = L.add(sizeof(uint64_t) * B);
+  const size_t oLo = L.add(sizeof(int32_t) * B);
+  const size_t oHi = L.add(sizeof(int32_t) * B);
+  const size_t oR = L.add(sizeof(double) * B);
+  const size_t in_bytes = L.size;
+  const size_t oG = L.add(sizeof(int32_t) * 3 * (size_t)B);  // the region records (device only)
+  char* h = s->pinned().get(in_bytes);
+  if (!h) return sfail(FDCN_ENOMEM, "hipHostMalloc(%zu) failed", in_bytes);
+  uint64_t* a = (uint64_t*)(h + oA);
+  uint64_t* f = (uint64_t*)(h + oF);
+  for (int32_t b = 0; b < B; ++b) {
+    a[b] = (uint64_t)s->slots.ptr[slots[b]];
+    f[b] = (uint64_t)s->slots.ptr[floor_slots[b]];
+  }
+  if (barrier) {
+    memcpy(h + oLo, ko_lo, sizeof(int32_t) * B);
+    memcpy(h + oHi, ko_hi, sizeof(int32_t) * B);
+    memcpy(h + oR, rebate, sizeof(double) * B);
+  }
+  hipStream_t st;
+  if ((rc = pick_stream(s, &st))) return rc;
+  // The ordering of fdcn_session_knockout: after everything the session has
+  // queued so far on every stream (the march that produced the slots, the
+  // upload of the floor, any earlier reader of the slots).
+  for (hipStream_t other : s->streams) {
+    if (other == st) continue;
+    int32_t ev;
+    if ((rc = record(s, other, &ev))) return rc;
+    S_TRY(hipStreamWaitEvent(st, s->events[ev], 0));
+  }
+  char* d = nullptr;
+  if ((rc = alloc_block(s, st, L.size, &d))) return rc;
+  S_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(exercise_kernel, dim3((unsigned)B), dim3(256), 0, st, n_nodes,
+                     (const uint64_t*)(d + oA), (const uint64_t*)(d + oF),
+                     barrier ? (const int32_t*)(d + oLo) : nullptr,
+                     barrier ? (const int32_t*)(d + oHi) : nullptr,
+                     barrier ? (const double*)(d + oR) : nullptr, (int32_t*)(d + oG));
+  S_TRY(hipGetLastError());
+  int32_t ev;
+  if ((rc = record(s, st, &ev))) return rc;
+  for (int32_t b = 0; b < B; ++b) s->slots.ev[(size_t)slots[b]] = ev;  // consumers wait for it
+  s->regions.add((int32_t*)(d + oG), B, ev, out_region_ids);
+  return FDCN_OK;
+}
+
+int fdcn_session_exercise_regions(fdcn_session* s, int32_t n, const int32_t* ids, int32_t* out) {
+  if (!s) return sfail(FDCN_EINVAL, "NULL session");
+  if (n < 0) return sfail(FDCN_EINVAL, "exercise_regions: n >= 0");
+  if (n == 0) return FDCN_OK;
+  if (!ids || !out) return sfail(FDCN_EINVAL, "exercise_regions: NULL argument");
+  char err[160];
+  if (s->regions.check(n, ids, err, sizeof(err))) return sfail(FDCN_EINVAL, "%s", err);
+  const size_t rec = sizeof(int32_t) * 3;
+  char* h = s->pinned().get(rec * (size_t)n);
+  if (!h) return sfail(FDCN_ENOMEM, "hipHostMalloc(%zu) failed", rec * (size_t)n);
+  hipStream_t st;
+  int rc = pick_stream(s, &st);
+  if (rc) return rc;
+  for (int32_t e : s->regions.producers(n, ids)) S_TRY(hipStreamWaitEvent(st, s->events[e], 0));
+  // consecutive ids of one call are consecutive records: one copy per run
+  for (int32_t i = 0; i < n;) {
+    int32_t k = i + 1;
+    while (k < n && s->regions.ev[(size_t)ids[k]] == s->regions.ev[(size_t)ids[k - 1]] &&
+           s->regions.ptr[(size_t)ids[k]] == s->regions.ptr[(size_t)ids[k - 1]] + 3)
+      ++k;
+    S_TRY(hipMemcpyAsync(h + rec * (size_t)i, s->regions.ptr[(size_t)ids[i]], rec * (size_t)(k - i),
+                         hipMemcpyDeviceToHost, st));
+    i = k;
+  }
+  S_TRY(hipStreamSynchronize(st));
+  memcpy(out, h, rec * (size_t)n);
   return FDCN_OK;
 }
 

@@ -8,6 +8,8 @@
 //   SlotTable     slot number -> device vector, its length and the event of
 //                 the launch that produced it; argument checks; the distinct
 //                 producer events a consumer must wait for
+//   RegionTable   exercise-region id -> its record on the device and the event
+//                 of the launch that writes it
 // Nothing here is thread-safe: a session belongs to one thread (fdcn.h).
 #ifndef FDCN_SESSION_BOOK_H
 #define FDCN_SESSION_BOOK_H
@@ -127,6 +129,47 @@ struct SlotTable {
     std::vector<int32_t> evs;
     evs.reserve((size_t)count);
     for (int32_t i = 0; i < count; ++i) evs.push_back(ev[(size_t)slots[i]]);
+    std::sort(evs.begin(), evs.end());
+    evs.erase(std::unique(evs.begin(), evs.end()), evs.end());
+    return evs;
+  }
+};
+
+// Exercise-region records (fdcn_session_exercise): id -> the record's three
+// ints (lo, hi, count) in device memory and the event of the launch that
+// writes them.  Ids are consecutive per session.
+struct RegionTable {
+  std::vector<int32_t*> ptr;
+  std::vector<int32_t> ev;
+
+  int32_t size() const { return (int32_t)ptr.size(); }
+
+  // B consecutive records of 3 ints from `base`, written by event `event`:
+  // their ids into out[B]
+  void add(int32_t* base, int32_t B, int32_t event, int32_t* out) {
+    for (int32_t b = 0; b < B; ++b) {
+      out[b] = size();
+      ptr.push_back(base + (size_t)3 * b);
+      ev.push_back(event);
+    }
+  }
+
+  // 0, or writes the reason to err and returns -1: an id outside the table
+  int check(int32_t count, const int32_t* ids, char* err, size_t errlen) const {
+    for (int32_t i = 0; i < count; ++i)
+      if (ids[i] < 0 || ids[i] >= size()) {
+        snprintf(err, errlen, "exercise region %d does not exist (session has %d)", ids[i],
+                 size());
+        return -1;
+      }
+    return 0;
+  }
+
+  // the distinct events that write the records `ids` (checked), ascending
+  std::vector<int32_t> producers(int32_t count, const int32_t* ids) const {
+    std::vector<int32_t> evs;
+    evs.reserve((size_t)count);
+    for (int32_t i = 0; i < count; ++i) evs.push_back(ev[(size_t)ids[i]]);
     std::sort(evs.begin(), evs.end());
     evs.erase(std::unique(evs.begin(), evs.end()), evs.end());
     return evs;

@@ -174,7 +174,10 @@ def contract_from_pricer(p, n_exercise: int = 64) -> LsmContract:
     `_monitor_taus`.  A pricer with a dividend in (valuation, maturity] is
     refused.  An `already_hit` pricer, and a knock-in that can never knock in,
     carry the pricer's own answer in `fixed_price` and are never launched; an
-    `already_in` pricer is the vanilla contract."""
+    `already_in` pricer is the vanilla contract.  A BermudanFDMPricer
+    (bermudan.py) gives its own exercise dates as `exercise_times`
+    (`n_exercise` is ignored); one with a monitoring date inside the life that
+    is not an exercise date is refused."""
     if p._div_times_tau():
         raise ValueError("cash dividends are not supported by the least-squares Monte Carlo.")
     if p.spot_snapped is None and p.strike_snapped is None:
@@ -193,6 +196,14 @@ def contract_from_pricer(p, n_exercise: int = 64) -> LsmContract:
     if bt != "none":
         taus, at_maturity = p._monitor_taus()
         mon = sorted(T - tau for tau in taus) + ([T] if at_maturity else [])
+    exercise = None
+    if hasattr(p, "_exercise_taus"):  # BermudanFDMPricer: its own exercise dates
+        ex_taus = {tau for tau, _ in p._exercise_taus()}
+        if bt != "none" and any(tau not in ex_taus for tau in p._monitor_taus()[0]):
+            raise ValueError("a monitoring date inside the life is not an exercise date: the "
+                             "least-squares Monte Carlo pays max(payoff, rebate) at every "
+                             "breach, the Bermudan FD rule only on a date that is both.")
+        exercise = sorted(T - tau for tau in ex_taus)
     c = plan_american_contract(
         spot=float(spot), strike=float(p._strike_for_pde()), vol=p.sigma,
         option_type=p.option_type, discount_rate=p.discount_rate_nacc,
@@ -200,7 +211,8 @@ def contract_from_pricer(p, n_exercise: int = 64) -> LsmContract:
         lower_barrier=getattr(p, "lower_barrier", None) if bt in _LOWER else None,
         upper_barrier=getattr(p, "upper_barrier", None) if bt in _UPPER else None,
         monitor_times=mon, rebate_amount=getattr(p, "rebate_amount", 0.0),
-        rebate_at_hit=getattr(p, "rebate_at_hit", False) and bt in _KO, n_exercise=n_exercise)
+        rebate_at_hit=getattr(p, "rebate_at_hit", False) and bt in _KO, n_exercise=n_exercise,
+        exercise_times=exercise)
     c.fixed_price = fixed
     return c
 

@@ -57,6 +57,10 @@ def _bind(L: ctypes.CDLL) -> None:
     L.fdcn_session_knockout.argtypes = [_V, _I, _I, _V, _V, _V, _V, _V]
     L.fdcn_session_knockin.restype = _I
     L.fdcn_session_knockin.argtypes = [_V, _I, _I, _V, _V, _V, _V]
+    L.fdcn_session_exercise.restype = _I
+    L.fdcn_session_exercise.argtypes = [_V, _I, _I, _V, _V, _V, _V, _V, _V]
+    L.fdcn_session_exercise_regions.restype = _I
+    L.fdcn_session_exercise_regions.argtypes = [_V, _I, _V, _V]
     L.fdcn_session_dividend_jump.restype = _I
     L.fdcn_session_dividend_jump.argtypes = [_V, _I, _I, _V, _V, _V, _V, _V]
     L.fdcn_session_greeks.restype = _I
@@ -295,6 +299,46 @@ class Session:
             raise ValueError("knockin: one threshold pair and source slot per slot")
         capi._check(self._L.fdcn_session_knockin(self._h, B, int(n_nodes), _ptr(sl), _ptr(ss),
                                                  _ptr(lo), _ptr(hi)))
+
+    def exercise(self, slots, n_nodes: int, floor_slots, ko_lo=None, ko_hi=None,
+                 rebate=None) -> np.ndarray:
+        """Bermudan exercise event in place on `slots` (fdcn_session_exercise):
+        nodes j <= ko_lo[b] or j >= ko_hi[b] of vector b become max(floor_j,
+        rebate[b]), every other node max(V_j, floor_j), with the floor vectors
+        in floor_slots (only read).  ko_lo, ko_hi and rebate all None: no
+        barrier.  Returns the ids of the vectors' exercise-region records
+        (exercise_regions)."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        B = sl.shape[0] if sl.ndim == 1 else -1
+        fs = np.ascontiguousarray(floor_slots, np.int32)
+        given = [x is not None for x in (ko_lo, ko_hi, rebate)]
+        if any(given) and not all(given):
+            raise ValueError("exercise: ko_lo, ko_hi and rebate go together (all or none)")
+        lo = hi = R = None
+        if all(given):
+            lo = np.ascontiguousarray(ko_lo, np.int32)
+            hi = np.ascontiguousarray(ko_hi, np.int32)
+            R = np.ascontiguousarray(rebate, np.float64)
+        if (sl.ndim != 1 or fs.shape != (B,)
+                or (lo is not None and (lo.shape != (B,) or hi.shape != (B,) or R.shape != (B,)))):
+            raise ValueError("exercise: one floor slot (and threshold pair and rebate) per slot")
+        out = np.empty(B, dtype=np.int32)
+        capi._check(self._L.fdcn_session_exercise(self._h, B, int(n_nodes), _ptr(sl), _ptr(fs),
+                                                  _ptr(lo), _ptr(hi), _ptr(R), _ptr(out)))
+        return out
+
+    def exercise_regions(self, ids) -> np.ndarray:
+        """[n, 3] int32 = lo, hi, count of the exercise-region records `ids`
+        (fdcn_session_exercise_regions): the nodes that were not knocked and
+        had floor_j > V_j before the event; (n_nodes, -1, 0) without any.
+        Synchronises."""
+        a = np.ascontiguousarray(ids, np.int32)
+        if a.ndim != 1:
+            raise ValueError("exercise_regions: ids must be a flat list")
+        out = np.empty((a.shape[0], 3), dtype=np.int32)
+        capi._check(self._L.fdcn_session_exercise_regions(self._h, a.shape[0], _ptr(a),
+                                                          _ptr(out)))
+        return out
 
     def dividend_jump(self, slots, s_nodes: np.ndarray, cash, strike_call) -> np.ndarray:
         sl = np.ascontiguousarray(slots, np.int32)

@@ -50,7 +50,8 @@ extern "C" {
  * after 7; fdcn_session_knockin (the American knock-in chain) joined later as
  * an additive symbol, with the version left at 8.  So did the least-squares
  * Monte Carlo entry points (fdcn_mc_lsm_batch, fdcn_mc_lsm_batch_dev,
- * fdcn_mc_lsm_plan).
+ * fdcn_mc_lsm_plan) and the Bermudan exercise event (fdcn_session_exercise,
+ * fdcn_session_exercise_regions).
  * 7: the BGK barrier pricer's Monte Carlo entry points (fdcn_mc_bgk_batch,
  * fdcn_mc_bgk_batch_dev, fdcn_mc_bgk_plan) were added after 6.
  * 6: the Monte Carlo discrete-barrier entry points (fdcn_mc_barrier_batch,
@@ -263,6 +264,34 @@ int fdcn_session_knockout(fdcn_session* s, int32_t B, int32_t n_nodes, const int
  * FDCN_ABI_VERSION (still 8); a caller that needs it looks the symbol up. */
 int fdcn_session_knockin(fdcn_session* s, int32_t B, int32_t n_nodes, const int32_t* slots,
                          const int32_t* src_slots, const int32_t* ko_lo, const int32_t* ko_hi);
+
+/* Exercise event of a Bermudan option, in place on `slots` [B] (no new slot),
+ * fused with the knock-out of a date that is also a monitoring date:
+ *   V_j <- max(floor_j, rebate[b])   for j <= ko_lo[b] or j >= ko_hi[b]
+ *   V_j <- max(V_j, floor_j)         on every other node
+ * with floor the vector in floor_slots[b] (the exercise value, only read).
+ * ko_lo, ko_hi and rebate all NULL: no barrier, no node is knocked; otherwise
+ * all three are given and the thresholds follow fdcn_session_knockout.
+ * Bit-identical to np.where(knocked, np.maximum(floor, R), np.maximum(V, floor))
+ * for finite inputs (on a tie either operand is kept: the same bits except for
+ * signed zeros); a NaN in either operand of a max gives NaN.
+ * out_region_ids [B] receives the id of one exercise-region record per vector,
+ * kept in session-owned device memory (ids are consecutive per session): lo,
+ * hi and count of the nodes that are not knocked and had floor_j > V_j before
+ * the event (a NaN compares false); without any, lo = n_nodes, hi = -1,
+ * count = 0.  Read them with fdcn_session_exercise_regions.
+ * Ordered as fdcn_session_knockout: after every call the session queued
+ * before it, and later consumers of `slots` wait for it.  B >= 1, n_nodes >= 1
+ * (the slots' length); a slot may appear once in `slots`, and no floor slot
+ * may be one of `slots`.  Additive: the two symbols joined the exported
+ * surface without a change of FDCN_ABI_VERSION (still 8). */
+int fdcn_session_exercise(fdcn_session* s, int32_t B, int32_t n_nodes, const int32_t* slots,
+                          const int32_t* floor_slots, const int32_t* ko_lo, const int32_t* ko_hi,
+                          const double* rebate, int32_t* out_region_ids);
+
+/* The exercise-region records `ids` [n] of this session into out [n][3] = lo,
+ * hi, count.  Waits for the events that write them (synchronises).  n >= 0. */
+int fdcn_session_exercise_regions(fdcn_session* s, int32_t n, const int32_t* ids, int32_t* out);
 
 /* fdcn_session_march for an Ikonen-Toivanen march (it != 0 required) whose
  * payoff lies in earlier slots (payoff_slots [B], e.g. from

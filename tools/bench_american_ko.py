@@ -33,6 +33,15 @@ time), the Crank-Nicolson march of U and the knock-in event U <- W, 22 of
 them.  Same clock as `chain`; the line then holds ki_chain, the knock-out
 `chain` of the same process and the plain launch (chain_host is left out),
 and --dump-outputs writes american_ki_prices.npy.
+
+--bermudan times the Bermudan chain instead (bermudan.py: the same trades as
+a put exercisable weekly, no barrier): five Crank-Nicolson segments with
+fdcn_session_exercise between them, beside the knock-out `chain` of the same
+process (same grid and batch, 23 Ikonen-Toivanen segments).  Same clock as
+`chain`; the line holds bermudan_chain, chain and the range of the exercised
+node counts per date.  A kernel trace of this mode shows exercise_kernel and
+knockout_kernel on the same shape; --dump-outputs writes bermudan_prices.npy
+and bermudan_regions.npy.
 """
 from __future__ import annotations
 
@@ -59,13 +68,21 @@ def weekdays():
     return [d for d in days if d.weekday() < 5]
 
 
+def weekly():
+    return [VAL + dt.timedelta(days=k) for k in (7, 14, 21, 28)]
+
+
 def build_jobs(B: int, n_space: int, n_time: int, barrier: float, seed: int = 0,
-               knock_in: bool = False):
+               knock_in: bool = False, bermudan: bool = False):
     """One grid job per scenario: a single pricer re-pointed at each trade of
     the sweep (same dates and curve), as bench.py builds the vanilla batch."""
     from finite_difference_amd import (AmericanBarrierFDMPricer, AmericanKnockInFDMPricer,
-                                       market)
+                                       BermudanFDMPricer, market)
     cls = AmericanKnockInFDMPricer if knock_in else AmericanBarrierFDMPricer
+    kw = dict(barrier_type="down-and-in" if knock_in else "down-and-out",
+              lower_barrier=barrier, monitor_dates=weekdays())
+    if bermudan:  # no barrier: the exercise event alone
+        cls, kw = BermudanFDMPricer, dict(exercise_dates=weekly())
     curve = market.iso_curve(market.create_rate_df(math.exp(0.07053828272) - 1.0))
     p, jobs = None, []
     for i in range(B):
@@ -76,9 +93,7 @@ def build_jobs(B: int, n_space: int, n_time: int, barrier: float, seed: int = 0,
             p = cls(
                 spot=SPOT, strike=strike, valuation_date=VAL, maturity_date=MAT, sigma=sigma,
                 option_type="put", discount_curve=curve, forward_curve=curve,
-                num_space_nodes=n_space, num_time_steps=n_time, rannacher_steps=2,
-                barrier_type="down-and-in" if knock_in else "down-and-out",
-                lower_barrier=barrier, monitor_dates=weekdays())
+                num_space_nodes=n_space, num_time_steps=n_time, rannacher_steps=2, **kw)
         p._reset_trade(SPOT, strike, sigma)
         p._build_log_grid()
         jobs.append(p._make_job(p._state_key(sigma, n_time), sigma, n_time))
@@ -209,6 +224,63 @@ def run_knockin_chain(p, jobs, gw, gu):
     return t_queued + t_wait, (t_queued, t_upload), out[:, 0].copy()
 
 
+def bermudan_groups(p, jobs):
+    """The launch group of every segment of the Bermudan chain (plain
+    Crank-Nicolson; all scenarios share pts / steps / restart)."""
+    from finite_difference_amd import capi
+    from finite_difference_amd.engine import Group, pack
+    j0 = jobs[0]
+    assert all(all(j[k] == j0[k] for k in ("pts", "steps", "restart")) for j in jobs)
+    solves = []
+    for j in jobs:
+        p.sigma = j["sigma"]
+        p._restore(j["grid"])
+        solves.extend(s for _, s in p._job_solves(j, 0))
+    g0 = pack(solves, list(range(len(solves))))
+    del solves
+    assert not g0.it
+
+    def variant(seg):
+        tau0, tau1, steps = j0["pts"][seg], j0["pts"][seg + 1], j0["steps"][seg]
+        P = g0.params.copy()
+        P[:, capi.P_DT] = (tau1 - tau0) / float(steps)
+        P[:, capi.P_TAU0] = tau0
+        return Group(False, g0.n_nodes, int(steps),
+                     p.rannacher_steps if j0["restart"][seg] else 0, P, g0.iparams, g0.v_init,
+                     g0.payoff, g0.mon_step, g0.mon_rebate, g0.index)
+    groups = [variant(s) for s in range(len(j0["steps"]))]
+    assert np.array_equal(groups[0].params, g0.params)
+    return groups
+
+
+def run_bermudan_chain(p, jobs, groups):
+    """run_chain for the Bermudan put: payoff uploaded once, the first march
+    starts from its slots, fdcn_session_exercise (no barrier) after every
+    segment but the last; the region records are read back at the end."""
+    from finite_difference_amd.session import GK_READOUT, Session
+    n = groups[0].n_nodes
+    assert all(j["v_is_payoff"] for j in jobs)
+    assert all(len(evs) == 1 and evs[0][0] == "ex" for j in jobs for evs in j["events"])
+    pay_host = groups[0].v_init  # the chain starts from the payoff
+    with Session() as S:
+        t0 = time.perf_counter()
+        pay = S.upload(pay_host)
+        t_upload = time.perf_counter() - t0
+        slots, ids = pay, []
+        for s, g in enumerate(groups):
+            slots = S.march(g, slots)
+            if s < len(groups) - 1:
+                ids.append(S.exercise(slots, n, pay))
+        t_queued = time.perf_counter() - t0
+        trades = [(GK_READOUT, [p._job_readout(j, int(sl), False)], ())
+                  for j, sl in zip(jobs, slots)]
+        t1 = time.perf_counter()
+        out = S.greeks(trades)  # waits for the chain
+        t_wait = time.perf_counter() - t1
+        regions = S.exercise_regions(np.concatenate(ids)).reshape(len(ids), len(jobs), 3)
+    return t_queued + t_wait, (t_queued, t_upload), out[:, 0].copy(), regions
+
+
 def run_plain(g, launches: int, warmup: int):
     import torch
     from finite_difference_amd import capi
@@ -266,6 +338,9 @@ def main() -> int:
     ap.add_argument("--knock-in", action="store_true",
                     help="time the knock-in chain (down-and-in at --barrier) beside the "
                          "knock-out chain and the plain launch")
+    ap.add_argument("--bermudan", action="store_true",
+                    help="time the Bermudan chain (a put exercisable weekly) beside the "
+                         "knock-out chain")
     args = ap.parse_args()
 
     from finite_difference_amd import capi
@@ -277,6 +352,8 @@ def main() -> int:
 
     if args.knock_in:
         return main_knock_in(args, p, jobs, groups, plain, t_plan)
+    if args.bermudan:
+        return main_bermudan(args, p, jobs, groups, t_plan)
     res = {}
     for name, ps in (("chain", True), ("chain_host", False)):
         runs = [run_chain(p, jobs, groups, ps) for _ in range(args.warmup + args.reps)]
@@ -363,6 +440,48 @@ def main_knock_in(args, p, jobs, groups, plain, t_plan: float) -> int:
         os.makedirs(args.dump_outputs, exist_ok=True)
         np.save(os.path.join(args.dump_outputs, "american_ki_prices.npy"), prices)
         line["dumped"] = {"american_ki_prices": list(prices.shape)}
+    print(json.dumps(line))
+    return 0 if line["parity"]["ok"] and line["all_finite"] else 3
+
+
+def main_bermudan(args, p, jobs, groups, t_plan: float) -> int:
+    t0 = time.perf_counter()
+    q, b_jobs = build_jobs(args.batch, args.n_space, args.n_time, args.barrier, bermudan=True)
+    gb = bermudan_groups(q, b_jobs)
+    t_plan += time.perf_counter() - t0
+
+    def spread(runs):
+        sec = [r[0] for r in runs]
+        return {"median": statistics.median(sec) * 1e3, "min": min(sec) * 1e3,
+                "max": max(sec) * 1e3,
+                "host_calls_ms": statistics.median([r[1][0] for r in runs]) * 1e3}
+    bm = [run_bermudan_chain(q, b_jobs, gb) for _ in range(args.warmup + args.reps)]
+    bm = bm[args.warmup:]
+    ko = [run_chain(p, jobs, groups, True) for _ in range(args.warmup + args.reps)]
+    ko = ko[args.warmup:]
+    prices, regions = bm[-1][2], bm[-1][3]
+    line = {
+        "metric": "bermudan_chain_ms",
+        "value": spread(bm)["median"],
+        "batch": args.batch, "n_space": args.n_space, "n_time": args.n_time,
+        "segments": len(gb), "segment_steps": [int(g.n_time) for g in gb],
+        "ko_segments": len(groups), "reps": args.reps, "warmup": args.warmup,
+        "bermudan_chain_ms": spread(bm),
+        "chain_ms": spread(ko),
+        "bermudan_over_chain": spread(bm)["median"] / spread(ko)["median"],
+        "plan_seconds": t_plan,
+        "parity": facade_parity(q, b_jobs, prices),
+        "all_finite": bool(np.all(np.isfinite(prices))),
+        "price_range": [float(prices.min()), float(prices.max())],
+        # per exercise date (tau ascending): the exercised node counts over the batch
+        "region_count_range": [[int(r[:, 2].min()), int(r[:, 2].max())] for r in regions],
+    }
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "bermudan_prices.npy"), prices)
+        np.save(os.path.join(args.dump_outputs, "bermudan_regions.npy"), regions)
+        line["dumped"] = {"bermudan_prices": list(prices.shape),
+                          "bermudan_regions": list(regions.shape)}
     print(json.dumps(line))
     return 0 if line["parity"]["ok"] and line["all_finite"] else 3
 

@@ -121,6 +121,28 @@ void test_slots() {
   CHECK(a[17] == 1.0 && b[9] == 4.0);
 }
 
+void test_regions() {
+  fdcn_book::RegionTable t;
+  std::vector<int32_t> a(3 * 3), b(3 * 2);
+  int32_t out[3];
+  t.add(a.data(), 3, 4, out);
+  CHECK(out[0] == 0 && out[2] == 2 && t.size() == 3 && t.ptr[2] == a.data() + 6);
+  t.add(b.data(), 2, 7, out);
+  CHECK(out[0] == 3 && out[1] == 4 && t.ev[4] == 7 && t.ptr[4] == b.data() + 3);
+  char err[160];
+  const int32_t ok[4] = {4, 0, 3, 0};
+  CHECK(t.check(4, ok, err, sizeof(err)) == 0);
+  const int32_t missing[2] = {1, 5};
+  CHECK(t.check(2, missing, err, sizeof(err)) == -1 && strstr(err, "does not exist"));
+  const int32_t neg[1] = {-1};
+  CHECK(t.check(1, neg, err, sizeof(err)) == -1);
+  const std::vector<int32_t> ev = t.producers(4, ok);
+  CHECK(ev.size() == 2 && ev[0] == 4 && ev[1] == 7);
+  CHECK(t.producers(0, ok).empty());
+  for (int32_t k = 0; k < t.size(); ++k) t.ptr[(size_t)k][2] = k;  // records address live memory
+  CHECK(a[5] == 1 && b[5] == 4);
+}
+
 }  // namespace
 
 int main() {
@@ -128,6 +150,7 @@ int main() {
   test_owns();
   test_arena();
   test_slots();
+  test_regions();
   printf("session_book_driver: ok\n");
   return 0;
 }
