@@ -3,7 +3,13 @@
 # Makefile adds the CPU sanitizer runs of SURVEY §5 on libfdcn's host code.
 #
 #   make lib        the in-tree libfdcn.so (same as __graft_entry__.build_lib)
-#   make sanitize   asan + tsan + host_call below (CPU only, no GPU needed)
+#   make sanitize   asan + tsan + host_call + qmc_check below (CPU only, no GPU
+#                   needed)
+#   make qmc_check  tools/sanitize/qmc_check_driver.cpp: the table checks of the
+#                   quasi-Monte Carlo path kernel (csrc/fdcn_qmc_table.h) under
+#                   ASan + UBSan: well-formed bridge and incremental tables of
+#                   every length, walked as the kernel walks them, and each
+#                   malformed table the header names
 #   make host_call  tools/sanitize/host_call_driver.cpp: the staging of the
 #                   host-array entry points (csrc/fdcn_host_call.h) under ASan
 #                   (leak check on) + UBSan, malloc / memcpy standing in for
@@ -34,14 +40,15 @@ TSAN := -Xarch_host -fsanitize=thread
 CSRC := finite_difference_amd/csrc
 HOST_SRCS := $(CSRC)/fdcn_host.hip $(CSRC)/fdcn_plan.hip
 HDRS := include/fdcn.h include/fdcn_diag.h $(CSRC)/fdcn_shared.h $(CSRC)/fdcn_session_book.h \
-        $(CSRC)/fdcn_host_call.h $(CSRC)/fdcn_philox.h
+        $(CSRC)/fdcn_host_call.h $(CSRC)/fdcn_philox.h $(CSRC)/fdcn_mc_path.h \
+        $(CSRC)/fdcn_qmc_table.h
 DEV_OBJS := build/obj/fdcn_kernels.o build/obj/fdcn_analytic.o build/obj/fdcn_session.o \
             build/obj/fdcn_vc.o build/obj/fdcn_mc.o build/obj/fdcn_mc_bgk.o \
-            build/obj/fdcn_mc_lsm.o
+            build/obj/fdcn_mc_lsm.o build/obj/fdcn_mc_qmc.o
 SAN_TESTS := tests/test_tau_sequence.py tests/test_capi_symbols.py tests/test_scenario_batch.py \
              tests/test_american_batch.py tests/test_barrier_host.py tests/test_american_host.py
 
-.PHONY: lib sanitize asan tsan host_call clean-sanitize
+.PHONY: lib sanitize asan tsan host_call qmc_check clean-sanitize
 
 lib:
 	$(PY) -c "import __graft_entry__ as g; g.build_lib()"
@@ -91,7 +98,16 @@ host_call: build/asan/host_call_driver
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	    ./build/asan/host_call_driver
 
-sanitize: asan tsan host_call
+build/asan/qmc_check_driver: tools/sanitize/qmc_check_driver.cpp $(CSRC)/fdcn_qmc_table.h
+	@mkdir -p build/asan
+	$(CXX) -std=c++17 -g -O1 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -fno-omit-frame-pointer -o $@ $<
+
+qmc_check: build/asan/qmc_check_driver
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
+	    ./build/asan/qmc_check_driver
+
+sanitize: asan tsan host_call qmc_check
 
 clean-sanitize:
 	rm -rf build/asan build/tsan

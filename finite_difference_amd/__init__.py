@@ -10,7 +10,8 @@ __version__ = "0.1.0"
 from . import capi  # noqa: F401
 from .engine import Engine, Solve, Boundary, default_engine  # noqa: F401
 from .mc_barrier import (NacaCurve, BarrierSpec, RebateSpec, MCConfig,  # noqa: F401
-                         price_discrete_barrier_mc, mc_barrier_batch, merge_mc_stats)
+                         price_discrete_barrier_mc, mc_barrier_batch, merge_mc_stats,
+                         merge_qmc_stats)
 from .bgk_barrier import DiscreteBarrierBGKPricer, bgk_price_batch  # noqa: F401
 from .american_barrier import AmericanBarrierFDMPricer  # noqa: F401
 from .american_knockin import AmericanKnockInFDMPricer  # noqa: F401

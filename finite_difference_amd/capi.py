@@ -48,11 +48,12 @@ EXPORTED = ("fdcn_cn_batch", "fdcn_it_batch", "fdcn_cn_batch_dev", "fdcn_it_batc
             "fdcn_vmath", "fdcn_american_plan", "fdcn_device_ordinals",
             "fdcn_mc_barrier_batch", "fdcn_mc_barrier_batch_dev", "fdcn_mc_plan",
             "fdcn_mc_bgk_batch", "fdcn_mc_bgk_batch_dev", "fdcn_mc_bgk_plan",
-            "fdcn_mc_lsm_batch", "fdcn_mc_lsm_batch_dev", "fdcn_mc_lsm_plan")
+            "fdcn_mc_lsm_batch", "fdcn_mc_lsm_batch_dev", "fdcn_mc_lsm_plan",
+            "fdcn_mc_qmc_batch", "fdcn_mc_qmc_batch_dev", "fdcn_mc_qmc_plan")
 # include/fdcn_diag.h: test / tuning entry points, not the product boundary
 DIAG_EXPORTED = ("fdcn_force_variant", "fdcn_forced_variant", "fdcn_variant_name",
                  "fdcn_vc_force_variant", "fdcn_vc_variant_name", "fdcn_vc_forms",
-                 "fdcn_mc_normals")
+                 "fdcn_mc_normals", "fdcn_qmc_normals")
 FLAVOUR_THROUGHPUT, FLAVOUR_LATENCY, FLAVOUR_PAIRED = 0, 1, 2
 VC_NDIAG = 6
 RR_NPARAM, RR_NFLAG = 8, 5
@@ -63,6 +64,7 @@ MC_P_SPOT, MC_P_STRIKE, MC_P_DF_T, MC_P_THRESHOLD, MC_P_REBATE, MC_P_FLOOR = ran
 MC_F_PUT, MC_F_KIND, MC_F_REBATE_AT_HIT, MC_F_DIV_FIRST, MC_F_STREAM = range(5)
 MC_S_DRIFT, MC_S_DIFF, MC_S_DIV, MC_S_MONITOR, MC_S_DF_END = range(5)
 MC_KIND = {"none": 0, "down-and-out": 1, "up-and-out": 2, "down-and-in": 3, "up-and-in": 4}
+QMC_MAX_STEPS = 64  # FDCN_QMC_MAX_STEPS
 # BGK pricer's Monte Carlo paths (enum fdcn_bgk_param / _flag / _step)
 BGK_MAX_G, BGK_NPARAM, BGK_NFLAG, BGK_NSTEP, BGK_NSTAT = 8, 7, 4, 4, 4
 (BGK_P_LOG_SPOT, BGK_P_STRIKE, BGK_P_UPPER, BGK_P_LOWER, BGK_P_EPS_BARRIER, BGK_P_EPS_PAYOFF,
@@ -293,6 +295,17 @@ def lib() -> ctypes.CDLL:
                                            ctypes.POINTER(ctypes.c_int64)]
             L.fdcn_mc_normals.restype = _I
             L.fdcn_mc_normals.argtypes = [_I64, _I, ctypes.c_uint64, _I, _I64, _V]
+            L.fdcn_mc_qmc_batch.restype = _I
+            L.fdcn_mc_qmc_batch.argtypes = [_I, _I, _I64, _I, _I, _I, _V, _V, _V, _V, _V, _V,
+                                            ctypes.c_uint64, _I64, _I, _V, _V, _V]
+            L.fdcn_mc_qmc_batch_dev.restype = _I
+            L.fdcn_mc_qmc_batch_dev.argtypes = [_I, _I, _I64, _I, _I, _I, _V, _V, _V, _V, _V, _V,
+                                                ctypes.c_uint64, _I64, _I, _V, _V, _V, _V, _I64, _V]
+            L.fdcn_mc_qmc_plan.restype = _I
+            L.fdcn_mc_qmc_plan.argtypes = [_I, _I64, _I, _PI, _PI, ctypes.POINTER(ctypes.c_int64)]
+            L.fdcn_qmc_normals.restype = _I
+            L.fdcn_qmc_normals.argtypes = [_I64, _I, _I, _I, _V, ctypes.c_uint64, _I, _I64, _I, _V,
+                                           _V]
             _lib = L
     return _lib
 
@@ -726,6 +739,99 @@ def mc_normals(n_obs: int, n_steps: int, seed: int, stream_id: int = 0,
     _check(lib().fdcn_mc_normals(int(n_obs), int(n_steps), int(seed) & (2 ** 64 - 1),
                                  int(stream_id), int(obs_first), z.ctypes.data))
     return z
+
+
+def mc_qmc_plan(n_steps: int, n_obs: int, R: int = 1) -> dict:
+    """Geometry of a quasi-Monte Carlo launch (fdcn_mc_qmc_plan; host only):
+    workgroups per (contract, replicate), observations per workgroup, threads
+    per workgroup, workspace bytes per contract."""
+    nb, per = ctypes.c_int32(), ctypes.c_int32()
+    ws = ctypes.c_int64()
+    _check(lib().fdcn_mc_qmc_plan(int(n_steps), int(n_obs), int(R), ctypes.byref(nb),
+                                  ctypes.byref(per), ctypes.byref(ws)))
+    return dict(blocks_per_replicate=nb.value, obs_per_block=per.value,
+                threads=per.value // 16, ws_bytes_per_contract=ws.value)
+
+
+def _qmc_tables(n_steps: int, B: int, dirnum, bridge_idx, bridge_w):
+    D = np.ascontiguousarray(dirnum, dtype=np.uint32)
+    X = _i32(bridge_idx)
+    W = _f64(bridge_w)
+    if D.shape != (n_steps, 32):
+        raise ValueError(f"mc_qmc_batch: dirnum must be [n_steps, 32] = {(n_steps, 32)}")
+    if X.shape != (n_steps, 3):
+        raise ValueError(f"mc_qmc_batch: bridge_idx must be [n_steps, 3] = {(n_steps, 3)}")
+    if W.shape != (B, n_steps, 3):
+        raise ValueError(f"mc_qmc_batch: bridge_w must be [B, n_steps, 3] = {(B, n_steps, 3)}")
+    return D, X, W
+
+
+def mc_qmc_batch(params, flags, step, n_obs: int, R: int, antithetic: bool, dirnum, bridge_idx,
+                 bridge_w, *, scramble: bool = True, seed: int = 0, obs_first: int = 0,
+                 rep_first: int = 0, want_payoffs: bool = False):
+    """fdcn_mc_qmc_batch on host arrays -> (stats [B, MC_NSTAT], rep [B, R, 2])
+    (price, stderr, sum m, sum m^2 over the replicate means; sum p, sum p^2 of
+    each replicate), plus payoffs [B, R, n_obs] with want_payoffs.  params,
+    flags, step as mc_barrier_batch; dirnum [n_steps, 32] uint32, bridge_idx
+    [n_steps, 3] int32, bridge_w [B, n_steps, 3] (include/fdcn.h)."""
+    require_device()
+    P = _f64(params).reshape(-1, MC_NPARAM)
+    F = _i32(flags).reshape(-1, MC_NFLAG)
+    S = _f64(step)
+    B = P.shape[0]
+    if F.shape[0] != B or S.ndim != 3 or S.shape[0] != B or S.shape[2] != MC_NSTEP:
+        raise ValueError("mc_qmc_batch: params [B, 6], flags [B, 5], step [B, n_steps, 5]")
+    n_steps, n_obs, R = S.shape[1], int(n_obs), int(R)
+    D, X, W = _qmc_tables(n_steps, B, dirnum, bridge_idx, bridge_w)
+    if n_obs < 1 or R < 1:
+        raise ValueError("mc_qmc_batch: n_obs and R must be >= 1")
+    stats = np.empty((B, MC_NSTAT), dtype=np.float64)
+    rep = np.empty((B, R, 2), dtype=np.float64)
+    pay = np.empty((B, R, n_obs), dtype=np.float64) if want_payoffs else None
+    _check(lib().fdcn_mc_qmc_batch(
+        B, n_steps, n_obs, R, 1 if antithetic else 0, 1 if scramble else 0, P.ctypes.data,
+        F.ctypes.data, S.ctypes.data, D.ctypes.data, X.ctypes.data, W.ctypes.data,
+        int(seed) & (2 ** 64 - 1), int(obs_first), int(rep_first), stats.ctypes.data,
+        rep.ctypes.data, pay.ctypes.data if want_payoffs else None))
+    return (stats, rep, pay) if want_payoffs else (stats, rep)
+
+
+def mc_qmc_batch_dev(B: int, n_steps: int, n_obs: int, R: int, antithetic: bool, scramble: bool,
+                     params_ptr: int, flags_ptr: int, step_ptr: int, dirnum_ptr: int, bridge_idx,
+                     bridge_w_ptr: int, seed: int, obs_first: int, rep_first: int, stats_ptr: int,
+                     rep_ptr: Optional[int], payoff_ptr: Optional[int],
+                     workspace_ptr: Optional[int], workspace_bytes: int,
+                     stream_ptr: Optional[int]) -> None:
+    """fdcn_mc_qmc_batch_dev: every array already on the device except
+    bridge_idx (a host array [n_steps, 3]); asynchronous on `stream_ptr`."""
+    X = _i32(bridge_idx)
+    if X.shape != (int(n_steps), 3):
+        raise ValueError(f"mc_qmc_batch_dev: bridge_idx must be [n_steps, 3] = {(n_steps, 3)}")
+    _check(lib().fdcn_mc_qmc_batch_dev(
+        int(B), int(n_steps), int(n_obs), int(R), 1 if antithetic else 0, 1 if scramble else 0,
+        params_ptr, flags_ptr, step_ptr, dirnum_ptr, X.ctypes.data, bridge_w_ptr,
+        int(seed) & (2 ** 64 - 1), int(obs_first), int(rep_first), stats_ptr, rep_ptr, payoff_ptr,
+        workspace_ptr, int(workspace_bytes), stream_ptr))
+
+
+def qmc_normals(n_obs: int, dirnum, *, R: int = 1, scramble: bool = True, seed: int = 0,
+                stream_id: int = 0, obs_first: int = 0, rep_first: int = 0):
+    """The points the quasi-Monte Carlo path kernel generates (diagnostics,
+    include/fdcn_diag.h) -> (words [R, n_obs, n_dims] uint32, y [R, n_obs,
+    n_dims]); dirnum [n_dims, 32] uint32."""
+    require_device()
+    D = np.ascontiguousarray(dirnum, dtype=np.uint32)
+    if D.ndim != 2 or D.shape[1] != 32:
+        raise ValueError("qmc_normals: dirnum must be [n_dims, 32]")
+    n_obs, R, n_dims = int(n_obs), int(R), D.shape[0]
+    if n_obs < 1 or R < 1:
+        raise ValueError("qmc_normals: n_obs and R must be >= 1")
+    words = np.empty((R, n_obs, n_dims), dtype=np.uint32)
+    y = np.empty((R, n_obs, n_dims), dtype=np.float64)
+    _check(lib().fdcn_qmc_normals(n_obs, n_dims, R, 1 if scramble else 0, D.ctypes.data,
+                                  int(seed) & (2 ** 64 - 1), int(stream_id), int(obs_first),
+                                  int(rep_first), words.ctypes.data, y.ctypes.data))
+    return words, y
 
 
 def mc_bgk_plan(n_obs: int, G: int = 1) -> dict:

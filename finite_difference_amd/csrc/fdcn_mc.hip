@@ -31,6 +31,7 @@
 
 #include "../../include/fdcn.h"
 #include "../../include/fdcn_diag.h"
+#include "fdcn_mc_path.h"
 #include "fdcn_philox.h"
 #include "fdcn_shared.h"
 
@@ -44,42 +45,11 @@ constexpr int kChunk = kThreads * kPerThread;  // observations per workgroup
 
 using fdcn_philox::normal_pair;  // Philox4x32-10 + Box-Muller (fdcn_philox.h)
 
-// ---- one path --------------------------------------------------------------
-struct Contract {
-  double spot, strike, df_T, thr, rebate, floor;
-  int kind;  // 0 none, 1 down-out, 2 up-out, 3 down-in, 4 up-in
-  bool put, down, rebate_at_hit, div_first;
-};
-
-struct Path {
-  double s, hit_df;
-  bool untouched;  // no monitored breach so far
-};
-
-// step row: drift, diff, cash dividend, monitor flag, df at the step's end
-__device__ __forceinline__ void advance(Path& p, const Contract& c, const double* __restrict__ st,
-                                        double z) {
-  p.s *= exp(st[0] + st[1] * z);
-  const double div = st[2];
-  if (c.div_first && div != 0.0) p.s = fmax(p.s - div, c.floor);
-  if (c.kind != 0 && st[3] != 0.0) {
-    const bool breached = c.down ? p.s <= c.thr : p.s >= c.thr;
-    if (breached && p.untouched) {
-      p.hit_df = st[4];  // the first hit's own discount factor
-      p.untouched = false;
-    }
-  }
-  if (!c.div_first && div != 0.0) p.s = fmax(p.s - div, c.floor);
-}
-
-__device__ __forceinline__ double payoff(const Path& p, const Contract& c) {
-  const double vanilla = c.put ? fmax(c.strike - p.s, 0.0) : fmax(p.s - c.strike, 0.0);
-  const double pv = c.df_T * vanilla;
-  if (c.kind == 0) return pv;
-  if (c.kind <= 2)  // knock-out: survivors the vanilla, the others the rebate
-    return p.untouched ? pv : c.rebate * (c.rebate_at_hit ? p.hit_df : c.df_T);
-  return p.untouched ? 0.0 : pv;  // knock-in
-}
+// ---- one path: Contract / Path / advance / payoff of fdcn_mc_path.h ----------
+using fdcn_mc_path::advance;
+using fdcn_mc_path::Contract;
+using fdcn_mc_path::Path;
+using fdcn_mc_path::payoff;
 
 struct McArgs {
   int32_t n_steps, n_blocks;
@@ -101,19 +71,7 @@ mc_path_kernel(McArgs a, const double* __restrict__ params, const int32_t* __res
   const double* P = params + (size_t)b * FDCN_MC_NPARAM;
   const int32_t* F = flags + (size_t)b * FDCN_MC_NFLAG;
   const double* S = step + (size_t)b * a.n_steps * FDCN_MC_NSTEP;
-  Contract c;
-  c.spot = P[FDCN_MC_P_SPOT];
-  c.strike = P[FDCN_MC_P_STRIKE];
-  c.df_T = P[FDCN_MC_P_DF_T];
-  c.thr = P[FDCN_MC_P_THRESHOLD];
-  c.rebate = P[FDCN_MC_P_REBATE];
-  c.floor = P[FDCN_MC_P_FLOOR];
-  c.put = F[FDCN_MC_F_PUT] != 0;
-  c.kind = F[FDCN_MC_F_KIND];
-  if (c.kind < 0 || c.kind > 4) c.kind = 0;  // _dev callers: the host entry rejects these
-  c.down = c.kind == 1 || c.kind == 3;
-  c.rebate_at_hit = F[FDCN_MC_F_REBATE_AT_HIT] != 0;
-  c.div_first = F[FDCN_MC_F_DIV_FIRST] != 0;
+  const Contract c = fdcn_mc_path::load_contract(P, F);
   const uint32_t stream = (uint32_t)F[FDCN_MC_F_STREAM];
 
   double sum = 0.0, sum2 = 0.0;
@@ -218,31 +176,6 @@ int check_sizes(int32_t B, int32_t n_steps, int64_t n_obs, int32_t antithetic) {
   return FDCN_OK;
 }
 
-int check_contracts(int32_t B, const double* params, const int32_t* flags) {
-  char msg[160];
-  for (int32_t b = 0; b < B; ++b) {
-    const int32_t* f = flags + (size_t)b * FDCN_MC_NFLAG;
-    const double* p = params + (size_t)b * FDCN_MC_NPARAM;
-    const char* bad = nullptr;
-    if (f[FDCN_MC_F_PUT] < 0 || f[FDCN_MC_F_PUT] > 1) bad = "flag put must be 0 or 1";
-    else if (f[FDCN_MC_F_KIND] < 0 || f[FDCN_MC_F_KIND] > 4) bad = "flag kind must be 0..4";
-    else if (f[FDCN_MC_F_REBATE_AT_HIT] < 0 || f[FDCN_MC_F_REBATE_AT_HIT] > 1)
-      bad = "flag rebate_at_hit must be 0 or 1";
-    else if (f[FDCN_MC_F_DIV_FIRST] < 0 || f[FDCN_MC_F_DIV_FIRST] > 1)
-      bad = "flag dividend_before_monitor must be 0 or 1";
-    else if (f[FDCN_MC_F_STREAM] < 0) bad = "flag stream id must be >= 0";
-    else if (!(p[FDCN_MC_P_SPOT] > 0.0)) bad = "spot must be positive";
-    else if (!(p[FDCN_MC_P_STRIKE] > 0.0)) bad = "strike must be positive";
-    else if (f[FDCN_MC_F_KIND] != 0 && !(p[FDCN_MC_P_THRESHOLD] > 0.0))
-      bad = "threshold must be positive where a barrier is set";
-    if (bad) {
-      snprintf(msg, sizeof msg, "mc_barrier_batch: contract %d: %s", b, bad);
-      return mfail(FDCN_EINVAL, msg);
-    }
-  }
-  return FDCN_OK;
-}
-
 int launch(int32_t B, int32_t n_steps, int64_t n_obs, int32_t antithetic, const double* params,
            const int32_t* flags, const double* step, const double* z, uint64_t seed,
            int64_t obs_first, double* stats, double* payoff_out, double* workspace,
@@ -266,6 +199,33 @@ int launch(int32_t B, int32_t n_steps, int64_t n_obs, int32_t antithetic, const 
 }
 
 }  // namespace
+
+// the per-contract checks of the host entries (also fdcn_mc_qmc_batch)
+int fdcn_internal::mc_check_contracts(const char* entry, int32_t B, const double* params,
+                                       const int32_t* flags) {
+  char msg[160];
+  for (int32_t b = 0; b < B; ++b) {
+    const int32_t* f = flags + (size_t)b * FDCN_MC_NFLAG;
+    const double* p = params + (size_t)b * FDCN_MC_NPARAM;
+    const char* bad = nullptr;
+    if (f[FDCN_MC_F_PUT] < 0 || f[FDCN_MC_F_PUT] > 1) bad = "flag put must be 0 or 1";
+    else if (f[FDCN_MC_F_KIND] < 0 || f[FDCN_MC_F_KIND] > 4) bad = "flag kind must be 0..4";
+    else if (f[FDCN_MC_F_REBATE_AT_HIT] < 0 || f[FDCN_MC_F_REBATE_AT_HIT] > 1)
+      bad = "flag rebate_at_hit must be 0 or 1";
+    else if (f[FDCN_MC_F_DIV_FIRST] < 0 || f[FDCN_MC_F_DIV_FIRST] > 1)
+      bad = "flag dividend_before_monitor must be 0 or 1";
+    else if (f[FDCN_MC_F_STREAM] < 0) bad = "flag stream id must be >= 0";
+    else if (!(p[FDCN_MC_P_SPOT] > 0.0)) bad = "spot must be positive";
+    else if (!(p[FDCN_MC_P_STRIKE] > 0.0)) bad = "strike must be positive";
+    else if (f[FDCN_MC_F_KIND] != 0 && !(p[FDCN_MC_P_THRESHOLD] > 0.0))
+      bad = "threshold must be positive where a barrier is set";
+    if (bad) {
+      snprintf(msg, sizeof msg, "%s: contract %d: %s", entry, b, bad);
+      return set_error(FDCN_EINVAL, msg);
+    }
+  }
+  return FDCN_OK;
+}
 
 extern "C" {
 
@@ -309,7 +269,7 @@ int fdcn_mc_barrier_batch(int32_t B, int32_t n_steps, int64_t n_obs, int32_t ant
   if (!flags) return mfail(FDCN_EINVAL, "mc_barrier_batch: flags is NULL");
   if (!step) return mfail(FDCN_EINVAL, "mc_barrier_batch: step is NULL");
   if (!stats) return mfail(FDCN_EINVAL, "mc_barrier_batch: stats is NULL");
-  rc = check_contracts(B, params, flags);
+  rc = fdcn_internal::mc_check_contracts("mc_barrier_batch", B, params, flags);
   if (rc) return rc;
   fdcn_internal::HostCall c("mc_barrier_batch");
   if ((rc = c.open())) return rc;

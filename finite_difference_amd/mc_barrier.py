@@ -16,6 +16,13 @@ reference's operation order (:193-222, :268-293); the paths run
   fallback and the timed CPU baseline.  ``rng="philox"`` restates the device
   generator in NumPy (philox_normals), so both engines can run one stream.
 
+``rng="sobol"`` (either engine) replaces the pseudo-random normals by
+quasi-Monte Carlo points: `replicates` digitally shifted copies of one Sobol
+point set, inverse-CDF normals, laid onto the path through a Brownian bridge
+(``construction="bridge"``) or step by step (``"incremental"``) -- qmc.py and
+csrc/fdcn_mc_qmc.hip, the contract in include/fdcn.h.  The standard error is
+that of the replicate means.  ``cfg.n_paths`` stays the total.
+
 A missing GPU under ``engine="hip"`` is an error, never a silent fallback.
 """
 from __future__ import annotations
@@ -27,7 +34,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import capi, market
+from . import capi, market, qmc
 
 _KINDS = ("none", "down-and-out", "up-and-out", "down-and-in", "up-and-in")
 _DOWN = ("down-and-out", "down-and-in")
@@ -255,9 +262,11 @@ def philox_normals(n_obs: int, n_steps: int, seed: int, stream_id: int = 0,
 # ---------------------------------------------------------------------------
 # engines
 # ---------------------------------------------------------------------------
-def host_payoffs(c: McContract, Z: np.ndarray) -> np.ndarray:
+def host_payoffs(c: McContract, Z: np.ndarray, increments: bool = False) -> np.ndarray:
     """Discounted payoff of each row of Z [n, n_steps] (one path per row), in
-    NumPy, with the reference's operations in the reference's order."""
+    NumPy, with the reference's operations in the reference's order.  With
+    `increments`, Z holds the scaled Brownian increments W[m] - W[m-1] of a
+    path construction (qmc.qmc_increments) and a step is s *= exp(drift + dW)."""
     P, F, S = c.params, c.flags, c.step
     spot, strike, df_T, thr, rebate, floor = (float(v) for v in P)
     kind = int(F[capi.MC_F_KIND])
@@ -267,7 +276,10 @@ def host_payoffs(c: McContract, Z: np.ndarray) -> np.ndarray:
     untouched = np.ones(n, dtype=bool)
     hit_df = np.full(n, df_T)
     for i in range(c.n_steps):
-        s *= np.exp(S[i, capi.MC_S_DRIFT] + S[i, capi.MC_S_DIFF] * Z[:, i])
+        if increments:
+            s *= np.exp(S[i, capi.MC_S_DRIFT] + Z[:, i])
+        else:
+            s *= np.exp(S[i, capi.MC_S_DRIFT] + S[i, capi.MC_S_DIFF] * Z[:, i])
         div = float(S[i, capi.MC_S_DIV])
         if div_first and div != 0.0:
             s = np.maximum(s - div, floor)
@@ -287,10 +299,11 @@ def host_payoffs(c: McContract, Z: np.ndarray) -> np.ndarray:
     return pv * ~untouched
 
 
-def _host_observations(c: McContract, Z: np.ndarray, antithetic: bool) -> np.ndarray:
+def _host_observations(c: McContract, Z: np.ndarray, antithetic: bool,
+                       increments: bool = False) -> np.ndarray:
     if antithetic:
-        return 0.5 * (host_payoffs(c, Z) + host_payoffs(c, -Z))
-    return host_payoffs(c, Z)
+        return 0.5 * (host_payoffs(c, Z, increments) + host_payoffs(c, -Z, increments))
+    return host_payoffs(c, Z, increments)
 
 
 def _stats(n: int, sum_p: float, sum_p2: float) -> Tuple[float, float]:
@@ -319,6 +332,125 @@ def merge_mc_stats(parts) -> Dict[str, float]:
     return {"price": price, "stderr": stderr, "n_observations": n, "sum_p": sp, "sum_p2": sp2}
 
 
+def _qmc_stats(n: int, rep_sum_p) -> Tuple[float, float, List[float]]:
+    """price, stderr and the replicate means of R replicates of n observations
+    each, in the order of the device's finalize kernel (include/fdcn.h)."""
+    means = [float(sp) / float(n) for sp in rep_sum_p]
+    R = len(means)
+    total = 0.0
+    for m in means:
+        total += m
+    price = total / float(R)
+    ss = 0.0
+    for m in means:
+        ss += (m - price) * (m - price)
+    stderr = math.sqrt(ss / float(R - 1) / float(R)) if R > 1 else 0.0
+    return price, stderr, means
+
+
+def merge_qmc_stats(parts) -> Dict[str, object]:
+    """Price and stderr of a quasi-Monte Carlo run from its shards, merged by
+    replicate id: tuples (replicate id, n, sum p, sum p^2), or result dicts of
+    mc_barrier_batch / price_discrete_barrier_mc under rng="sobol".  Shards of
+    one replicate (disjoint observation ranges) add; distinct ids are
+    independent replicates.  Every replicate must end with the same n."""
+    acc: Dict[int, List[float]] = {}
+    for part in parts:
+        if isinstance(part, dict):
+            rows = zip(part["replicate_ids"], [part["observations_per_replicate"]] *
+                       len(part["replicate_ids"]), part["rep_sum_p"], part["rep_sum_p2"])
+        else:
+            rows = [part]
+        for rid, n, sp, sp2 in rows:
+            a = acc.setdefault(int(rid), [0, 0.0, 0.0])
+            a[0] += int(n)
+            a[1] += float(sp)
+            a[2] += float(sp2)
+    if not acc:
+        raise ValueError("merge_qmc_stats: no replicates")
+    ids = sorted(acc)
+    ns = {acc[k][0] for k in ids}
+    if len(ns) != 1 or min(ns) <= 0:
+        raise ValueError("merge_qmc_stats: the replicates hold different numbers of observations")
+    n = ns.pop()
+    price, stderr, _ = _qmc_stats(n, [acc[k][1] for k in ids])
+    return {"price": price, "stderr": stderr, "replicates": len(ids), "replicate_ids": ids,
+            "observations_per_replicate": n, "n_observations": n * len(ids),
+            "rep_sum_p": [acc[k][1] for k in ids], "rep_sum_p2": [acc[k][2] for k in ids]}
+
+
+def qmc_tables(group: Sequence[McContract], construction: str):
+    """(dirnum [n_steps, 32], bridge_idx [n_steps, 3], bridge_w [B, n_steps, 3])
+    of a launch: the order is shared, the weights follow each contract's DIFF
+    column (its variance clock)."""
+    n_steps = group[0].n_steps
+    if n_steps > qmc.MAX_STEPS:
+        raise ValueError(f"rng='sobol' takes at most {qmc.MAX_STEPS} steps (got {n_steps})")
+    idx, ws = None, []
+    for c in group:
+        diff = c.step[:, capi.MC_S_DIFF]
+        idx, w = qmc.bridge_plan(qmc.var_times(diff), construction, diff=diff)
+        ws.append(w)
+    return qmc.direction_numbers(n_steps), idx, np.stack(ws)
+
+
+def simulate_qmc(group: Sequence[McContract], n_obs: int, antithetic: bool, *,
+                 engine: str = "hip", seed: int = 0, stream_ids: Optional[Sequence[int]] = None,
+                 obs_first: int = 0, replicates: int = 16, rep_first: int = 0,
+                 construction: str = "bridge", scramble: bool = True,
+                 chunk_size: Optional[int] = None, want_payoffs: bool = False):
+    """Observations obs_first .. obs_first + n_obs - 1 of replicates rep_first
+    .. rep_first + replicates - 1 for contracts that share n_steps.  Returns
+    rep [B, R, 2] = sum p, sum p^2 of each replicate (and payoffs [B, R, n_obs]
+    with want_payoffs).  Both engines perform the operations of include/fdcn.h
+    (fdcn_mc_qmc_batch) in its order."""
+    if engine not in ("hip", "host"):
+        raise ValueError("engine must be 'hip' or 'host'")
+    if construction not in qmc.CONSTRUCTIONS:
+        raise ValueError(f"construction must be one of {qmc.CONSTRUCTIONS}")
+    B, n_obs, R = len(group), int(n_obs), int(replicates)
+    obs_first, rep_first = int(obs_first), int(rep_first)
+    n_steps = group[0].n_steps
+    if any(c.n_steps != n_steps for c in group):
+        raise ValueError("simulate: the contracts of a launch share n_steps")
+    ids = list(range(B)) if stream_ids is None else [int(s) for s in stream_ids]
+    if len(ids) != B:
+        raise ValueError("simulate: one stream id per contract")
+    if n_obs < 1 or R < 1 or obs_first < 0 or rep_first < 0:
+        raise ValueError("simulate: observations and replicates must be non-empty ranges")
+    if not scramble and R != 1:
+        raise ValueError("simulate: without the digital shift there is one replicate")
+    if obs_first + n_obs > 2 ** qmc.TABLE_BITS:
+        raise ValueError(f"rng='sobol': observation indices must stay below 2^{qmc.TABLE_BITS} "
+                         f"(the direction-number table has {qmc.TABLE_BITS} bits)")
+    dirnum, idx, BW = qmc_tables(group, construction)
+    if engine == "hip":
+        capi.require_device()
+        P, F, S = _stack(group, ids)
+        out = capi.mc_qmc_batch(P, F, S, n_obs, R, antithetic, dirnum, idx, BW,
+                                scramble=scramble, seed=seed, obs_first=obs_first,
+                                rep_first=rep_first, want_payoffs=want_payoffs)
+        return (out[1], out[2]) if want_payoffs else out[1]
+    rep = np.zeros((B, R, 2))
+    pay = np.empty((B, R, n_obs)) if want_payoffs else None
+    chunk = max(1, int(chunk_size or n_obs))
+    for lo in range(0, n_obs, chunk):
+        m = min(chunk, n_obs - lo)
+        words = qmc.sobol_words(m, dirnum, obs_first + lo)
+        for b, c in enumerate(group):
+            shifts = (qmc.digital_shifts(n_steps, range(rep_first, rep_first + R), seed, ids[b])
+                      if scramble else np.zeros((1, n_steps), dtype=np.uint32))
+            for k in range(R):
+                y = qmc.as241(qmc.uniforms(words ^ shifts[k][None, :]))
+                p = _host_observations(c, qmc.qmc_increments(y, idx, BW[b]), antithetic,
+                                       increments=True)
+                rep[b, k, 0] += float(np.sum(p))
+                rep[b, k, 1] += float(np.sum(p * p))
+                if want_payoffs:
+                    pay[b, k, lo:lo + m] = p
+    return (rep, pay) if want_payoffs else rep
+
+
 def _stack(group: Sequence[McContract], stream_ids: Sequence[int]):
     P = np.stack([c.params for c in group])
     F = np.stack([c.flags for c in group]).astype(np.int32)
@@ -330,9 +462,12 @@ def _stack(group: Sequence[McContract], stream_ids: Sequence[int]):
 def simulate(group: Sequence[McContract], n_obs: int, antithetic: bool, *, engine: str = "hip",
              rng: str = "philox", seed: int = 0, chunk_size: Optional[int] = None,
              stream_ids: Optional[Sequence[int]] = None, obs_first: int = 0, z=None,
-             want_payoffs: bool = False):
+             want_payoffs: bool = False, replicates: int = 16, construction: str = "bridge",
+             rep_first: int = 0):
     """Run n_obs observations of contracts that share n_steps.  Returns
     sums [B, 2] = sum p, sum p^2 (and payoffs [B, n_obs] with want_payoffs).
+    rng="sobol" runs n_obs observations of each of `replicates` replicates and
+    returns simulate_qmc's per-replicate sums [B, R, 2] (payoffs [B, R, n_obs]).
 
     Normals: `z` [n_obs, n_steps] if given; else rng="numpy" draws
     default_rng(seed).standard_normal((m, n_steps)) per chunk of `chunk_size`
@@ -340,8 +475,15 @@ def simulate(group: Sequence[McContract], n_obs: int, antithetic: bool, *, engin
     rng="philox" is the stream (seed, stream id) from observation obs_first."""
     if engine not in ("hip", "host"):
         raise ValueError("engine must be 'hip' or 'host'")
-    if rng not in ("philox", "numpy"):
-        raise ValueError("rng must be 'philox' or 'numpy'")
+    if rng not in ("philox", "numpy", "sobol"):
+        raise ValueError("rng must be 'philox', 'numpy' or 'sobol'")
+    if rng == "sobol":
+        if z is not None:
+            raise ValueError("simulate: rng='sobol' generates its own normals")
+        return simulate_qmc(group, n_obs, antithetic, engine=engine, seed=seed,
+                            stream_ids=stream_ids, obs_first=obs_first, replicates=replicates,
+                            rep_first=rep_first, construction=construction,
+                            chunk_size=chunk_size, want_payoffs=want_payoffs)
     B = len(group)
     n_steps = group[0].n_steps
     if any(c.n_steps != n_steps for c in group):
@@ -414,6 +556,33 @@ def _result(c: McContract, cfg: MCConfig, n_obs: int, sum_p: float, sum_p2: floa
     }
 
 
+def _qmc_result(c: McContract, cfg: MCConfig, n_rep: int, rep_ids: Sequence[int],
+                rep_sums: np.ndarray, construction: str) -> dict:
+    """The reference's keys with the replicate estimator: stderr is that of the
+    replicate means; n_observations counts all replicates."""
+    price, stderr, _ = _qmc_stats(n_rep, rep_sums[:, 0])
+    res = _result(c, cfg, n_rep * len(rep_ids), 0.0, 0.0)
+    res.update(price=float(price), stderr=float(stderr),
+               ci_95=(float(price - 1.96 * stderr), float(price + 1.96 * stderr)),
+               replicates=len(rep_ids), construction=construction,
+               replicate_ids=[int(r) for r in rep_ids], observations_per_replicate=int(n_rep),
+               rep_sum_p=[float(v) for v in rep_sums[:, 0]],
+               rep_sum_p2=[float(v) for v in rep_sums[:, 1]])
+    return res
+
+
+def _qmc_split(cfg: MCConfig, replicates: int) -> int:
+    """Observations per replicate: cfg.n_paths stays the total."""
+    replicates = int(replicates)
+    if replicates < 2:
+        raise ValueError("rng='sobol' needs replicates >= 2 (the stderr is that of the "
+                         "replicate means)")
+    n_rep = _n_observations(cfg) // replicates
+    if n_rep < 1:
+        raise ValueError("cfg.n_paths gives fewer than one observation per replicate")
+    return n_rep
+
+
 def _default_rng(engine: str, rng: Optional[str]) -> str:
     return rng if rng is not None else ("philox" if engine == "hip" else "numpy")
 
@@ -426,16 +595,25 @@ def price_discrete_barrier_mc(*, spot: float, strike: float, vol: float, option_
                               barrier: BarrierSpec = BarrierSpec("none"),
                               rebate: RebateSpec = RebateSpec(), cfg: MCConfig = MCConfig(),
                               include_maturity_monitor: bool = True, engine: str = "hip",
-                              rng: Optional[str] = None) -> Dict[str, object]:
+                              rng: Optional[str] = None, replicates: int = 16,
+                              construction: str = "bridge") -> Dict[str, object]:
     """Monte Carlo price of a discretely monitored single-barrier option: the
     reference's function, keys and errors, on the chosen engine (module
     docstring).  rng defaults to "philox" on the GPU (stream id 0) and to
-    "numpy" on the host."""
+    "numpy" on the host.  rng="sobol": `replicates` shifted Sobol point sets of
+    observations // replicates points each through `construction`; the result
+    adds "replicates", "construction" and the per-replicate sums."""
     c = plan_contract(spot=spot, strike=strike, vol=vol, option_type=option_type,
                       valuation=valuation, maturity=maturity, discount_curve=discount_curve,
                       forward_curve=forward_curve, dividends=dividends,
                       monitor_dates=monitor_dates, barrier=barrier, rebate=rebate, cfg=cfg,
                       include_maturity_monitor=include_maturity_monitor)
+    if _default_rng(engine, rng) == "sobol":
+        n_rep = _qmc_split(cfg, replicates)
+        reps = simulate_qmc([c], n_rep, bool(cfg.antithetic), engine=engine, seed=cfg.seed,
+                            stream_ids=[0], replicates=replicates, construction=construction,
+                            chunk_size=cfg.chunk_size)
+        return _qmc_result(c, cfg, n_rep, range(int(replicates)), reps[0], construction)
     n_obs = _n_observations(cfg)
     sums = simulate([c], n_obs, bool(cfg.antithetic), engine=engine,
                     rng=_default_rng(engine, rng), seed=cfg.seed, chunk_size=cfg.chunk_size,
@@ -446,7 +624,9 @@ def price_discrete_barrier_mc(*, spot: float, strike: float, vol: float, option_
 def mc_barrier_batch(contracts: Sequence[dict], cfg: MCConfig = MCConfig(), *,
                      engine: str = "hip", rng: Optional[str] = None,
                      stream_ids: Optional[Sequence[int]] = None,
-                     obs_range: Optional[range] = None) -> List[dict]:
+                     obs_range: Optional[range] = None, replicates: int = 16,
+                     construction: str = "bridge",
+                     rep_range: Optional[range] = None) -> List[dict]:
     """Price many contracts, one launch per distinct n_steps.  `contracts`:
     the keyword arguments of price_discrete_barrier_mc (without cfg, engine,
     rng) per contract; cfg is shared.  The Philox stream id of a contract is
@@ -454,18 +634,31 @@ def mc_barrier_batch(contracts: Sequence[dict], cfg: MCConfig = MCConfig(), *,
     range within [0, n_obs)) runs that part of every contract's observations
     only -- a rank's shard, or the rest of a resumed run -- which continues
     the same Philox streams; merge_mc_stats combines the parts.  Results, in
-    input order: the reference's dict plus "sum_p" and "sum_p2"."""
+    input order: the reference's dict plus "sum_p" and "sum_p2".
+    rng="sobol": `replicates` replicates of observations // replicates points;
+    obs_range then lies within one replicate's observations and `rep_range`
+    (within range(replicates)) picks the replicates a shard runs;
+    merge_qmc_stats combines the parts by replicate id."""
     rng = _default_rng(engine, rng)
     plans = [plan_contract(cfg=cfg, **kw) for kw in contracts]
-    n_total = _n_observations(cfg)
+    sobol = rng == "sobol"
+    if rep_range is not None and not sobol:
+        raise ValueError("rep_range needs rng='sobol'")
+    n_total = _qmc_split(cfg, replicates) if sobol else _n_observations(cfg)
+    r_lo, r_hi = 0, int(replicates)
+    if sobol and rep_range is not None:
+        r_lo, r_hi = rep_range.start, rep_range.stop
+        if rep_range.step != 1 or not 0 <= r_lo < r_hi <= int(replicates):
+            raise ValueError("rep_range must be a non-empty contiguous range within "
+                             "range(replicates)")
     lo, hi = 0, n_total
     if obs_range is not None:
         lo, hi = obs_range.start, obs_range.stop
         if obs_range.step != 1 or not 0 <= lo < hi <= n_total:
             raise ValueError("obs_range must be a non-empty contiguous range within the "
                              "contract's observations")
-        if rng != "philox" and (lo, hi) != (0, n_total):
-            raise ValueError("obs_range needs rng='philox' (a counter-based stream)")
+        if rng == "numpy" and (lo, hi) != (0, n_total):
+            raise ValueError("obs_range needs rng='philox' or 'sobol' (a counter-based stream)")
     ids = list(range(len(plans))) if stream_ids is None else [int(s) for s in stream_ids]
     if len(ids) != len(plans):
         raise ValueError("one stream id per contract")
@@ -474,6 +667,15 @@ def mc_barrier_batch(contracts: Sequence[dict], cfg: MCConfig = MCConfig(), *,
     for k, c in enumerate(plans):
         by_steps.setdefault(c.n_steps, []).append(k)
     for members in by_steps.values():
+        if sobol:
+            reps = simulate_qmc([plans[k] for k in members], hi - lo, bool(cfg.antithetic),
+                                engine=engine, seed=cfg.seed, chunk_size=cfg.chunk_size,
+                                stream_ids=[ids[k] for k in members], obs_first=lo,
+                                replicates=r_hi - r_lo, rep_first=r_lo, construction=construction)
+            for row, k in enumerate(members):
+                out[k] = _qmc_result(plans[k], cfg, hi - lo, range(r_lo, r_hi), reps[row],
+                                     construction)
+            continue
         sums = simulate([plans[k] for k in members], hi - lo, bool(cfg.antithetic), engine=engine,
                         rng=rng, seed=cfg.seed, chunk_size=cfg.chunk_size,
                         stream_ids=[ids[k] for k in members], obs_first=lo)

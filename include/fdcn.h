@@ -51,7 +51,9 @@ extern "C" {
  * an additive symbol, with the version left at 8.  So did the least-squares
  * Monte Carlo entry points (fdcn_mc_lsm_batch, fdcn_mc_lsm_batch_dev,
  * fdcn_mc_lsm_plan) and the Bermudan exercise event (fdcn_session_exercise,
- * fdcn_session_exercise_regions).
+ * fdcn_session_exercise_regions), and the quasi-Monte Carlo paths
+ * (fdcn_mc_qmc_batch, fdcn_mc_qmc_batch_dev, fdcn_mc_qmc_plan; fdcn_qmc_normals
+ * in fdcn_diag.h).
  * 7: the BGK barrier pricer's Monte Carlo entry points (fdcn_mc_bgk_batch,
  * fdcn_mc_bgk_batch_dev, fdcn_mc_bgk_plan) were added after 6.
  * 6: the Monte Carlo discrete-barrier entry points (fdcn_mc_barrier_batch,
@@ -520,6 +522,92 @@ int fdcn_mc_barrier_batch_dev(int32_t B, int32_t n_steps, int64_t n_obs, int32_t
  * output pointer may be NULL.  Host only. */
 int fdcn_mc_plan(int64_t n_obs, int32_t* blocks_per_contract, int32_t* obs_per_block,
                  int64_t* ws_bytes_per_contract);
+
+/* ---- Quasi-Monte Carlo paths of the same pricer (csrc/fdcn_mc_qmc.hip) ------
+ * fdcn_mc_qmc_batch prices the contracts of fdcn_mc_barrier_batch (the same
+ * params / flags / step arrays and enums, the same path functional) on R
+ * randomised replicates of n_obs Sobol points each, the normals laid onto the
+ * path through a caller-supplied construction table.  An additive symbol:
+ * FDCN_ABI_VERSION is still 8.  Every number below is a contract, evaluated in
+ * fp64 with each operation rounded separately.
+ *
+ * Observation o = obs_first + i (o < 2^32), replicate rho = rep_first + k.
+ * Sobol word of dimension j = 0 .. n_steps - 1:
+ *   g   = o ^ (o >> 1)                                   (Gray-code order)
+ *   w_j = XOR over the set bits k of g of dirnum[j][k]
+ *   dirnum [n_steps][32] uint32, left-aligned (bit 31 is 1/2), supplied by the
+ *   caller; the library embeds no table.  With a table of the usual
+ *   Joe-Kuo kind, point o is the o-th unscrambled draw of the sequence.
+ * Digital shift (scramble = 1):
+ *   w_j ^= x0 of Philox4x32-10(counter = (j, rho, 0, stream id),
+ *                              key = (seed & 0xffffffff, seed >> 32)),
+ *   the block function of fdcn_mc_barrier_batch above, stream id =
+ *   flags[FDCN_MC_F_STREAM].  scramble = 0 applies no shift; it requires R = 1
+ *   and reports stderr 0.
+ * Uniform:  u = ((double)w_j + 0.5) * 2^-32, never 0 or 1; 1 - u is exact.
+ * Normal:   y_j = Phi^-1(u) by Wichura's algorithm AS241, routine PPND16, with
+ *   the branches, constants and Horner order of CPython's
+ *   statistics._normal_dist_inv_cdf: q = u - 0.5; for |q| <= 0.425 a rational
+ *   function in 0.180625 - q^2 times q (no transcendental: bit for bit the
+ *   same in any IEEE arithmetic); otherwise r = sqrt(-log(min(u, 1 - u))),
+ *   r <= 5: rational in r - 1.6, else rational in r - 5; negated for q < 0.
+ * Path construction:
+ *   bridge_idx [n_steps][3] int32 = target, left, right -- shared by the
+ *               launch, always host memory (it reaches the kernel by value);
+ *   bridge_w   [B][n_steps][3]    = wl, wr, sd -- per contract;
+ *   W[0] = 0;  for j = 0 .. n_steps - 1:
+ *     W[target_j] = (wl_j * W[left_j] + wr_j * W[right_j]) + sd_j * y_j;
+ *   step m = 1 .. n_steps:  s *= exp(DRIFT_m + (W[m] - W[m-1])), then the
+ *   dividend, monitor test and hit discount factor of fdcn_mc_barrier_batch.
+ *   The DIFF column is not read.  With antithetic != 0 the mirrored path walks
+ *   -W and the observation is 0.5 * (f(W) + f(-W)).
+ * Reduction.  One workgroup owns one (contract, replicate, chunk of
+ * observations); the chunk (fdcn_mc_qmc_plan) is a function of n_steps and
+ * n_obs only.  Each thread adds its observations in index order, the workgroup
+ * reduces in a fixed tree, a second kernel adds the partials of a replicate in
+ * block order and combines the replicates in replicate order.  No
+ * floating-point atomics: a contract's numbers depend on neither B nor its
+ * position in the batch.  With m_rho = (sum p of replicate rho) / n_obs:
+ *   stats [B][FDCN_MC_NSTAT] = price = (sum m_rho) / R,
+ *                              stderr = sqrt(sum (m_rho - price)^2 / (R-1) / R)
+ *                                       (0 for R = 1),
+ *                              sum m_rho, sum m_rho^2
+ *   rep_out [B][R][2]          sum p, sum p^2 of each replicate (NULL: not written)
+ *   payoff_out [B][R][n_obs]   the observations (NULL: not written)
+ * Sharding.  Disjoint rep_first ranges are independent replicates; disjoint
+ * obs_first ranges of one replicate continue one point set.  The per-replicate
+ * sums of the parts add.
+ * Validation (before any device call; FDCN_EINVAL): B, n_obs or R < 1; n_steps
+ * outside 1 .. FDCN_QMC_MAX_STEPS; antithetic or scramble not 0 / 1;
+ * scramble == 0 with R != 1; obs_first < 0, obs_first + n_obs > 2^32,
+ * rep_first < 0; a NULL params / flags / step / dirnum / bridge_idx /
+ * bridge_w / stats; a workspace that is too small; a bridge_idx row that
+ * breaks one of: target in 1 .. n_steps, each target once; left < target and
+ * already defined (0 or an earlier target); right > target and already
+ * defined, or right == left (an extension past the known range: row 0 of a
+ * bridge, every row of an incremental construction).  Host entry only: the
+ * per-contract checks of fdcn_mc_barrier_batch and a non-finite bridge_w. */
+#define FDCN_QMC_MAX_STEPS 64
+/* Host pointers; copies in and out on the calling thread's stream and waits. */
+int fdcn_mc_qmc_batch(int32_t B, int32_t n_steps, int64_t n_obs, int32_t R, int32_t antithetic,
+                      int32_t scramble, const double* params, const int32_t* flags,
+                      const double* step, const uint32_t* dirnum, const int32_t* bridge_idx,
+                      const double* bridge_w, uint64_t seed, int64_t obs_first, int32_t rep_first,
+                      double* stats, double* rep_out, double* payoff_out);
+/* Device pointers except bridge_idx (host), asynchronous on `stream`, no host
+ * sync.  `workspace`: device scratch of at least B * ws_bytes_per_contract
+ * (fdcn_mc_qmc_plan) bytes, or NULL: allocated stream-ordered for the call. */
+int fdcn_mc_qmc_batch_dev(int32_t B, int32_t n_steps, int64_t n_obs, int32_t R, int32_t antithetic,
+                          int32_t scramble, const double* params, const int32_t* flags,
+                          const double* step, const uint32_t* dirnum, const int32_t* bridge_idx,
+                          const double* bridge_w, uint64_t seed, int64_t obs_first,
+                          int32_t rep_first, double* stats, double* rep_out, double* payoff_out,
+                          double* workspace, int64_t workspace_bytes, void* stream);
+/* Geometry of a launch: workgroups per (contract, replicate), observations per
+ * workgroup (256 threads x 16 up to 30 steps, 64 x 16 above), workspace bytes
+ * per contract.  Any output pointer may be NULL.  Host only. */
+int fdcn_mc_qmc_plan(int32_t n_steps, int64_t n_obs, int32_t R, int32_t* blocks_per_replicate,
+                     int32_t* obs_per_block, int64_t* ws_bytes_per_contract);
 
 /* ---- Monte Carlo paths of the BGK barrier pricer (csrc/fdcn_mc_bgk.hip) ----
  * fdcn_mc_bgk_batch <- DiscreteBarrierBGKPricer._mc_out_price's path functional

@@ -62,6 +62,17 @@ int fdcn_vc_forms(int32_t B, int32_t n_nodes, int32_t n_time, int32_t n_ranna,
 int fdcn_mc_normals(int64_t n_obs, int32_t n_steps, uint64_t seed, int32_t stream_id,
                     int64_t obs_first, double* z);
 
+/* The generator of fdcn_mc_qmc_batch alone (include/fdcn.h: Sobol word,
+ * digital shift, uniform, AS241; the same device functions): replicates
+ * rep_first .. rep_first + R - 1 of observations obs_first .. obs_first +
+ * n_obs - 1 in n_dims <= 64 dimensions, the shift drawn for `stream_id`.
+ * words_out [R][n_obs][n_dims] the shifted words, y_out [R][n_obs][n_dims]
+ * the normals (host memory; either may be NULL).  dirnum [n_dims][32].  The
+ * range checks of fdcn_mc_qmc_batch apply. */
+int fdcn_qmc_normals(int64_t n_obs, int32_t n_dims, int32_t R, int32_t scramble,
+                     const uint32_t* dirnum, uint64_t seed, int32_t stream_id, int64_t obs_first,
+                     int32_t rep_first, uint32_t* words_out, double* y_out);
+
 #ifdef __cplusplus
 }
 #endif

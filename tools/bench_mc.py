@@ -18,6 +18,14 @@ operations per path-step are a static count of the kernel's inner loop
 (tools/isa_stats.py FILE.s --kernel mc_path_kernelILb1ELb1E: one iteration is
 one Philox block, one Box-Muller pair and four path-steps), an FMA as two.
 
+--rng sobol times, after the Philox kernel and in the same process, the same
+workload through the quasi-Monte Carlo kernel (csrc/fdcn_mc_qmc.hip,
+fdcn_mc_qmc_batch_dev): `--replicates` shifted Sobol point sets of
+obs / replicates points each, Brownian-bridge construction, antithetic -- the
+same number of path-steps -- and reports it under "qmc" beside the Philox
+figure, with each kernel's mean standard error over the batch.  The default,
+--rng philox, runs and prints what it always did.
+
 Prints one JSON line.  --dump-outputs DIR writes the prices of the last
 timed launch as DIR/mc_stats.npy.  Without a GPU it fails; there is no
 fallback.
@@ -102,6 +110,58 @@ def device_run(plans, n_obs: int, launches: int, warmup: int, seed: int):
     return times, stats.cpu().numpy(), torch.cuda.get_device_name(0)
 
 
+def device_run_qmc(plans, n_obs: int, replicates: int, launches: int, warmup: int, seed: int):
+    """The Philox run's workload on the quasi-Monte Carlo kernel: n_obs //
+    replicates points in each of `replicates` replicates."""
+    import torch
+    from finite_difference_amd import capi, mc_barrier
+    dev = torch.device("cuda:0")
+    B, n_steps = len(plans), plans[0].n_steps
+    n_rep = n_obs // replicates
+    P, F, S = mc_barrier._stack(plans, list(range(B)))
+    dirnum, idx, bw = mc_barrier.qmc_tables(plans, "bridge")
+    dP, dF, dS, dW = (torch.from_numpy(a).to(dev) for a in (P, F, S, bw))
+    dD = torch.from_numpy(dirnum.view(np.int32)).to(dev)
+    stats = torch.zeros((B, capi.MC_NSTAT), dtype=torch.float64, device=dev)
+    ws_bytes = capi.mc_qmc_plan(n_steps, n_rep, replicates)["ws_bytes_per_contract"] * B
+    ws = torch.zeros(ws_bytes // 8, dtype=torch.float64, device=dev)
+    stream = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+
+    def launch():
+        capi.mc_qmc_batch_dev(B, n_steps, n_rep, replicates, True, True, dP.data_ptr(),
+                              dF.data_ptr(), dS.data_ptr(), dD.data_ptr(), idx, dW.data_ptr(), seed,
+                              0, 0, stats.data_ptr(), None, None, ws.data_ptr(), ws_bytes,
+                              stream.cuda_stream)
+    times = []
+    with torch.cuda.stream(stream):
+        for _ in range(warmup):
+            launch()
+        stream.synchronize()
+        for _ in range(launches):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(stream)
+            launch()
+            t1.record(stream)
+            t1.synchronize()
+            times.append(t0.elapsed_time(t1) * 1e-3)
+    return times, stats.cpu().numpy(), n_rep
+
+
+def parity_qmc(plans, stats, n_rep: int, replicates: int, seed: int, count: int = 2):
+    """The timed launch's prices for the first contracts against the host
+    engine on the same points (qmc.py)."""
+    from finite_difference_amd import mc_barrier
+    worst = 0.0
+    for b in range(count):
+        reps = mc_barrier.simulate_qmc([plans[b]], n_rep, True, engine="host", seed=seed,
+                                       stream_ids=[b], replicates=replicates, chunk_size=1 << 15)
+        want = mc_barrier._qmc_stats(n_rep, reps[0, :, 0])[0]
+        worst = max(worst, abs(float(stats[b, 0]) - want) / max(abs(want), 1e-300))
+    return {"contracts": count, "worst_rel_price_diff": worst, "bound": 1e-9,
+            "ok": bool(worst <= 1e-9)}
+
+
 def parity(plans, stats, n_obs: int, seed: int, count: int = 2):
     """The timed launch's own prices for the first contracts against the host
     engine on the same Philox streams (NumPy restatement of the generator)."""
@@ -144,6 +204,9 @@ def main() -> int:
     ap.add_argument("--host-contracts", type=int, default=16)
     ap.add_argument("--host-paths", type=int, default=1 << 20)
     ap.add_argument("--dump-outputs", default="", metavar="DIR")
+    ap.add_argument("--rng", choices=("philox", "sobol"), default="philox",
+                    help="sobol: also time the quasi-Monte Carlo kernel on the same workload")
+    ap.add_argument("--replicates", type=int, default=16, help="with --rng sobol")
     args = ap.parse_args()
 
     plans = build_batch(args.contracts)
@@ -180,12 +243,29 @@ def main() -> int:
         "parity": parity(plans, stats, args.obs, args.seed),
         "price_range": [float(stats[:, 0].min()), float(stats[:, 0].max())],
     }
+    ok = line["parity"]["ok"]
+    if args.rng == "sobol":
+        q_times, q_stats, n_rep = device_run_qmc(plans, args.obs, args.replicates, args.launches,
+                                                 args.warmup, args.seed)
+        q_med = statistics.median(q_times)
+        q_rate = args.contracts * n_rep * args.replicates * 2 * n_steps / q_med
+        line["qmc"] = {
+            "metric": "mc_qmc_path_steps_per_s", "value": q_rate, "rng": "sobol",
+            "construction": "bridge", "replicates": args.replicates, "obs_per_replicate": n_rep,
+            "launch_seconds": {"median": q_med, "min": min(q_times), "max": max(q_times)},
+            "relative_to_philox": q_rate / rate,
+            "mean_stderr": float(q_stats[:, 1].mean()),
+            "philox_mean_stderr": float(stats[:, 1].mean()),
+            "stderr_ratio_philox_over_sobol": float(stats[:, 1].mean() / q_stats[:, 1].mean()),
+            "parity": parity_qmc(plans, q_stats, n_rep, args.replicates, args.seed),
+        }
+        ok = ok and line["qmc"]["parity"]["ok"]
     if args.dump_outputs:
         os.makedirs(args.dump_outputs, exist_ok=True)
         np.save(os.path.join(args.dump_outputs, "mc_stats.npy"), stats)
         line["dumped"] = {"mc_stats": list(stats.shape)}
     print(json.dumps(line))
-    return 0 if line["parity"]["ok"] else 3
+    return 0 if ok else 3
 
 
 if __name__ == "__main__":
