@@ -49,6 +49,7 @@ EXPORTED = ("fdcn_cn_batch", "fdcn_it_batch", "fdcn_cn_batch_dev", "fdcn_it_batc
             "fdcn_mc_barrier_batch", "fdcn_mc_barrier_batch_dev", "fdcn_mc_plan",
             "fdcn_mc_bgk_batch", "fdcn_mc_bgk_batch_dev", "fdcn_mc_bgk_plan",
             "fdcn_mc_lsm_batch", "fdcn_mc_lsm_batch_dev", "fdcn_mc_lsm_plan",
+            "fdcn_mc_lsm_div_batch", "fdcn_mc_lsm_div_batch_dev",
             "fdcn_mc_qmc_batch", "fdcn_mc_qmc_batch_dev", "fdcn_mc_qmc_plan")
 # include/fdcn_diag.h: test / tuning entry points, not the product boundary
 DIAG_EXPORTED = ("fdcn_force_variant", "fdcn_forced_variant", "fdcn_variant_name",
@@ -289,6 +290,13 @@ def lib() -> ctypes.CDLL:
             L.fdcn_mc_lsm_batch_dev.restype = _I
             L.fdcn_mc_lsm_batch_dev.argtypes = [_I, _I, _I, _I, _V, _V, _V, ctypes.c_uint64, _I64,
                                                 _V, _V, _V, _V, _I64, _V]
+            L.fdcn_mc_lsm_div_batch.restype = _I
+            L.fdcn_mc_lsm_div_batch.argtypes = [_I, _I, _I, _I, _V, _V, _V, _V, ctypes.c_uint64,
+                                                _I64, _V, _V, _V]
+            L.fdcn_mc_lsm_div_batch_dev.restype = _I
+            L.fdcn_mc_lsm_div_batch_dev.argtypes = [_I, _I, _I, _I, _V, _V, _V, _V,
+                                                    ctypes.c_uint64, _I64, _V, _V, _V, _V, _I64,
+                                                    _V]
             L.fdcn_mc_lsm_plan.restype = _I
             L.fdcn_mc_lsm_plan.argtypes = [_I, _I, _I, _PI, ctypes.POINTER(ctypes.c_int64),
                                            ctypes.POINTER(ctypes.c_int64),
@@ -903,10 +911,12 @@ def mc_lsm_plan(n_steps: int, G: int, antithetic: bool) -> dict:
 
 
 def mc_lsm_batch(params, flags, step, G: int, antithetic: bool, *, seed: int = 0,
-                 obs_first: int = 0, want_values: bool = False, want_coef: bool = False):
+                 obs_first: int = 0, want_values: bool = False, want_coef: bool = False,
+                 div=None):
     """fdcn_mc_lsm_batch on host arrays -> (stats [B, LSM_NSTAT], values
     [B, G * LSM_SUBRUN] or None, coef [B, G, n_steps, LSM_NCOEF] or None).
-    params [B, LSM_NPARAM], flags [B, LSM_NFLAG], step [B, n_steps, LSM_NSTEP]."""
+    params [B, LSM_NPARAM], flags [B, LSM_NFLAG], step [B, n_steps, LSM_NSTEP].
+    With div [B, n_steps] (cash dividends on the path): fdcn_mc_lsm_div_batch."""
     require_device()
     P = _f64(params).reshape(-1, LSM_NPARAM)
     F = _i32(flags).reshape(-1, LSM_NFLAG)
@@ -918,10 +928,19 @@ def mc_lsm_batch(params, flags, step, G: int, antithetic: bool, *, seed: int = 0
     stats = np.empty((B, LSM_NSTAT), dtype=np.float64)
     val = np.empty((B, G * LSM_SUBRUN), dtype=np.float64) if want_values else None
     coef = np.empty((B, G, n_steps, LSM_NCOEF), dtype=np.float64) if want_coef else None
-    _check(lib().fdcn_mc_lsm_batch(
-        B, n_steps, G, 1 if antithetic else 0, P.ctypes.data, F.ctypes.data, S.ctypes.data,
-        int(seed) & (2 ** 64 - 1), int(obs_first), stats.ctypes.data,
-        val.ctypes.data if want_values else None, coef.ctypes.data if want_coef else None))
+    tail = (int(seed) & (2 ** 64 - 1), int(obs_first), stats.ctypes.data,
+            val.ctypes.data if want_values else None, coef.ctypes.data if want_coef else None)
+    if div is None:
+        _check(lib().fdcn_mc_lsm_batch(
+            B, n_steps, G, 1 if antithetic else 0, P.ctypes.data, F.ctypes.data, S.ctypes.data,
+            *tail))
+    else:
+        D = _f64(div)
+        if D.shape != (B, n_steps):
+            raise ValueError("mc_lsm_batch: div [B, n_steps]")
+        _check(lib().fdcn_mc_lsm_div_batch(
+            B, n_steps, G, 1 if antithetic else 0, P.ctypes.data, F.ctypes.data, S.ctypes.data,
+            D.ctypes.data, *tail))
     return stats, val, coef
 
 
@@ -936,3 +955,16 @@ def mc_lsm_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, params_ptr:
         int(B), int(n_steps), int(G), 1 if antithetic else 0, params_ptr, flags_ptr, step_ptr,
         int(seed) & (2 ** 64 - 1), int(obs_first), stats_ptr, values_ptr, coef_ptr, workspace_ptr,
         int(workspace_bytes), stream_ptr))
+
+
+def mc_lsm_div_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, params_ptr: int,
+                         flags_ptr: int, step_ptr: int, div_ptr: int, seed: int, obs_first: int,
+                         stats_ptr: int, values_ptr: Optional[int], coef_ptr: Optional[int],
+                         workspace_ptr: Optional[int], workspace_bytes: int,
+                         stream_ptr: Optional[int]) -> None:
+    """fdcn_mc_lsm_div_batch_dev: mc_lsm_batch_dev with the dividend rows
+    div [B, n_steps] on the device."""
+    _check(lib().fdcn_mc_lsm_div_batch_dev(
+        int(B), int(n_steps), int(G), 1 if antithetic else 0, params_ptr, flags_ptr, step_ptr,
+        div_ptr, int(seed) & (2 ** 64 - 1), int(obs_first), stats_ptr, values_ptr, coef_ptr,
+        workspace_ptr, int(workspace_bytes), stream_ptr))

@@ -5,7 +5,8 @@
 // american_barrier.py, american_knockin.py); the algorithm, the event rules and
 // the Philox mapping are the contract of include/fdcn.h (fdcn_mc_lsm_batch).
 //
-//   lsm_kernel<ANTI>     one workgroup = one sub-run = kSubrun paths of one
+//   lsm_kernel<ANTI, DIV>
+//                        one workgroup = one sub-run = kSubrun paths of one
 //                        contract, kPerThread per thread, all path state in
 //                        registers.  Phase A walks the fit set forward (first
 //                        breach step per path), phase B walks it backward
@@ -23,6 +24,13 @@
 // across the workgroup and read with scalar loads.  No floating-point atomics;
 // multiply and add are rounded separately (contraction off), so the NumPy host
 // engine (mc_american.py) differs only through exp / log and summation order.
+//
+// DIV = true (fdcn_mc_lsm_div_batch): a step may pay a cash dividend D_m, read
+// from the row div[b][n_steps] with scalar loads like the step table, so the
+// branch on D_m != 0 is uniform.  The spot goes through g(s) = s - D (s >= 2 D),
+// s / 2 (below) after the move in phases A and C and through g's inverse before
+// the backward move in phase B: no per-path state is added.  DIV = false is the
+// kernel without any of it.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -63,6 +71,21 @@ __device__ __forceinline__ double payoff(const Contract& c, double s) {
 
 __device__ __forceinline__ bool breach(const Contract& c, double s) {
   return (c.has_lo && s <= c.lower) || (c.has_hi && s >= c.upper);
+}
+
+// The dividend map on the log-spot and its inverse (include/fdcn.h).  g is
+// continuous at 2 D, so a rounding that takes the other branch on the way back
+// moves x by rounding error only.
+constexpr double kLn2 = 0.6931471805599453094;
+
+__device__ __forceinline__ double div_forward(double x, double d) {
+  const double s = exp(x);
+  return s >= 2.0 * d ? log(s - d) : x - kLn2;
+}
+
+__device__ __forceinline__ double div_backward(double x, double d) {
+  const double s = exp(x);
+  return s >= d ? log(s + d) : x + kLn2;
 }
 
 __device__ __forceinline__ double cubic(const double* c, double u) {
@@ -111,11 +134,12 @@ __device__ __forceinline__ bool solve_cubic(const double* s, const double* t, do
   return true;
 }
 
-template <bool ANTI>
+template <bool ANTI, bool DIV>
 __global__ void __launch_bounds__(kThreads)
 lsm_kernel(LsmArgs a, const double* __restrict__ params, const int32_t* __restrict__ flags,
            const double* __restrict__ step, double* __restrict__ ws,
-           double* __restrict__ values_out, double* __restrict__ coef_out) {
+           double* __restrict__ values_out, double* __restrict__ coef_out,
+           const double* __restrict__ div) {
   constexpr int kObs = ANTI ? kPerThread / 2 : kPerThread;  // observations per thread
   constexpr int kSigns = ANTI ? 2 : 1;
   const int b = blockIdx.x / a.G;  // contract
@@ -125,6 +149,7 @@ lsm_kernel(LsmArgs a, const double* __restrict__ params, const int32_t* __restri
   const double* P = params + (size_t)b * FDCN_LSM_NPARAM;
   const int32_t* F = flags + (size_t)b * FDCN_LSM_NFLAG;
   const double* S = step + (size_t)b * M * FDCN_LSM_NSTEP;
+  const double* D = DIV ? div + (size_t)b * M : nullptr;  // uniform, like S
   Contract c;
   c.strike = P[FDCN_LSM_P_STRIKE];
   c.lower = P[FDCN_LSM_P_LOWER];
@@ -164,6 +189,7 @@ lsm_kernel(LsmArgs a, const double* __restrict__ params, const int32_t* __restri
     const double dr1 = r1[FDCN_LSM_S_DRIFT], df1 = r1[FDCN_LSM_S_DIFF];
     const bool mon0 = kind != 0 && r0[FDCN_LSM_S_MONITOR] != 0.0;
     const bool mon1 = kind != 0 && r1[FDCN_LSM_S_MONITOR] != 0.0;
+    const double dv0 = DIV ? D[i] : 0.0, dv1 = DIV && two ? D[i + 1] : 0.0;
 #pragma unroll
     for (int j = 0; j < kObs; ++j) {
       double z0, z1;
@@ -172,9 +198,11 @@ lsm_kernel(LsmArgs a, const double* __restrict__ params, const int32_t* __restri
       for (int sg = 0; sg < kSigns; ++sg) {
         const int k = kSigns * j + sg;
         x[k] += dr0 + df0 * (sg ? -z0 : z0);
+        if (DIV && dv0 != 0.0) x[k] = div_forward(x[k], dv0);
         if (mon0 && h[k] > M && breach(c, exp(x[k]))) h[k] = i + 1;
         if (two) {
           x[k] += dr1 + df1 * (sg ? -z1 : z1);
+          if (DIV && dv1 != 0.0) x[k] = div_forward(x[k], dv1);
           if (mon1 && h[k] > M && breach(c, exp(x[k]))) h[k] = i + 2;
         }
       }
@@ -262,6 +290,7 @@ lsm_kernel(LsmArgs a, const double* __restrict__ params, const int32_t* __restri
     const double dr = r[FDCN_LSM_S_DRIFT], df = r[FDCN_LSM_S_DIFF];
     const double dfs = r[FDCN_LSM_S_DF_STEP];
     const int i = m - 1;
+    const double dv = DIV ? D[i] : 0.0;
     const bool fresh = (i & 1) || i == M - 1;  // else z0 of the pair drawn for step i + 1
 #pragma unroll
     for (int j = 0; j < kObs; ++j) {
@@ -277,6 +306,7 @@ lsm_kernel(LsmArgs a, const double* __restrict__ params, const int32_t* __restri
 #pragma unroll
       for (int sg = 0; sg < kSigns; ++sg) {
         const int k = kSigns * j + sg;
+        if (DIV && dv != 0.0) x[k] = div_backward(x[k], dv);
         x[k] -= dr + df * (sg ? -z : z);
         cf[k] *= dfs;
       }
@@ -314,6 +344,10 @@ lsm_kernel(LsmArgs a, const double* __restrict__ params, const int32_t* __restri
           const double* r = S + (size_t)(m - 1) * FDCN_LSM_NSTEP;
           const double* cc = coef[m - 1];
           x[k] += r[FDCN_LSM_S_DRIFT] + r[FDCN_LSM_S_DIFF] * (sg ? -zz[hf] : zz[hf]);
+          if (DIV) {
+            const double dv = D[m - 1];
+            if (dv != 0.0) x[k] = div_forward(x[k], dv);
+          }
           const bool mon = kind != 0 && r[FDCN_LSM_S_MONITOR] != 0.0;
           const bool fitted = m < M && r[FDCN_LSM_S_EXERCISE] != 0.0 && cc[4] != 0.0;
           if (!(mon || fitted || m == M) || done[k]) continue;
@@ -471,21 +505,37 @@ int check_contracts(int32_t B, int32_t n_steps, const double* params, const int3
   return FDCN_OK;
 }
 
+// every dividend finite and >= 0 (a dividend on the last step is legal)
+int check_dividends(int32_t B, int32_t n_steps, const double* div) {
+  char msg[200];
+  for (int32_t b = 0; b < B; ++b)
+    for (int32_t m = 0; m < n_steps; ++m) {
+      const double d = div[(size_t)b * n_steps + m];
+      if (isfinite(d) && d >= 0.0) continue;
+      snprintf(msg, sizeof msg, "mc_lsm_div_batch: contract %d: the dividend of step %d %s", b,
+               m + 1, isfinite(d) ? "is negative" : "is not finite");
+      return lfail(FDCN_EINVAL, msg);
+    }
+  return FDCN_OK;
+}
+
 int64_t ws_bytes(int32_t G) { return (int64_t)G * kWsRow * (int64_t)sizeof(double); }
 
 int launch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic, const double* params,
            const int32_t* flags, const double* step, uint64_t seed, int64_t obs_first,
            double* stats, double* values_out, double* coef_out, double* workspace,
-           hipStream_t stream) {
+           hipStream_t stream, const double* div = nullptr) {
   LsmArgs a;
   a.n_steps = n_steps;
   a.G = G;
   a.obs_first = obs_first;
   a.seed = seed;
   const dim3 grid((uint32_t)((int64_t)B * G)), block(kThreads);
-  auto fn = antithetic ? lsm_kernel<true> : lsm_kernel<false>;
+  // the div entries always run a DIV instance, an all-zero row included
+  auto fn = div ? (antithetic ? lsm_kernel<true, true> : lsm_kernel<false, true>)
+                : (antithetic ? lsm_kernel<true, false> : lsm_kernel<false, false>);
   hipLaunchKernelGGL(fn, grid, block, 0, stream, a, params, flags, step, workspace, values_out,
-                     coef_out);
+                     coef_out, div);
   if (hipGetLastError() != hipSuccess) return lfail(FDCN_EHIP, "mc_lsm_batch: launch failed");
   hipLaunchKernelGGL(lsm_finalize_kernel, dim3((B + kThreads - 1) / kThreads), block, 0, stream,
                      B, G, workspace, stats);
@@ -550,6 +600,55 @@ int fdcn_mc_lsm_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
     return launch(B, n_steps, G, antithetic, c.dev<double>(rP), c.dev<int32_t>(rF),
                   c.dev<double>(rS), seed, obs_first, c.dev<double>(rO), c.dev<double>(rY),
                   c.dev<double>(rC), c.dev<double>(rW), stream);
+  });
+}
+
+int fdcn_mc_lsm_div_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                              const double* params, const int32_t* flags, const double* step,
+                              const double* div, uint64_t seed, int64_t obs_first, double* stats,
+                              double* values_out, double* coef_out, double* workspace,
+                              int64_t workspace_bytes, void* stream) {
+  int rc = check_sizes(B, n_steps, G, antithetic, obs_first);
+  if (rc) return rc;
+  rc = check_pointers("mc_lsm_div_batch_dev", params, flags, step, stats);
+  if (rc) return rc;
+  if (!div) return lfail(FDCN_EINVAL, "mc_lsm_div_batch_dev: div is NULL");
+  return fdcn_call::with_workspace<fdcn_internal::HipCall>(
+      "mc_lsm_div_batch_dev", "this launch needs (fdcn_mc_lsm_plan)", workspace, workspace_bytes,
+      ws_bytes(G) * B, (hipStream_t)stream, [&](void* ws) {
+        return launch(B, n_steps, G, antithetic, params, flags, step, seed, obs_first, stats,
+                      values_out, coef_out, (double*)ws, (hipStream_t)stream, div);
+      });
+}
+
+int fdcn_mc_lsm_div_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                          const double* params, const int32_t* flags, const double* step,
+                          const double* div, uint64_t seed, int64_t obs_first, double* stats,
+                          double* values_out, double* coef_out) {
+  int rc = check_sizes(B, n_steps, G, antithetic, obs_first);
+  if (rc) return rc;
+  rc = check_pointers("mc_lsm_div_batch", params, flags, step, stats);
+  if (rc) return rc;
+  if (!div) return lfail(FDCN_EINVAL, "mc_lsm_div_batch: div is NULL");
+  rc = check_contracts(B, n_steps, params, flags, step);
+  if (rc) return rc;
+  rc = check_dividends(B, n_steps, div);
+  if (rc) return rc;
+  fdcn_internal::HostCall c("mc_lsm_div_batch");
+  if ((rc = c.open())) return rc;
+  const size_t nb = (size_t)B;
+  const int rP = c.in(params, sizeof(double) * nb * FDCN_LSM_NPARAM);
+  const int rF = c.in(flags, sizeof(int32_t) * nb * FDCN_LSM_NFLAG);
+  const int rS = c.in(step, sizeof(double) * nb * (size_t)n_steps * FDCN_LSM_NSTEP);
+  const int rD = c.in(div, sizeof(double) * nb * (size_t)n_steps);
+  const int rO = c.out(stats, sizeof(double) * nb * FDCN_LSM_NSTAT);
+  const int rY = c.out(values_out, sizeof(double) * nb * (size_t)G * kSubrun);
+  const int rC = c.out(coef_out, sizeof(double) * nb * (size_t)G * n_steps * FDCN_LSM_NCOEF);
+  const int rW = c.scratch((size_t)ws_bytes(G) * nb);
+  return c.run([&](hipStream_t stream) {
+    return launch(B, n_steps, G, antithetic, c.dev<double>(rP), c.dev<int32_t>(rF),
+                  c.dev<double>(rS), seed, obs_first, c.dev<double>(rO), c.dev<double>(rY),
+                  c.dev<double>(rC), c.dev<double>(rW), stream, c.dev<double>(rD));
   });
 }
 

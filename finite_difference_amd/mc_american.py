@@ -11,8 +11,13 @@ R = barrier.rebate_value -- and may be exercised before it.  A knock-in path
 may be exercised from its hit step on, that step included, and is paid the
 rebate at maturity if it never knocked in (american_knockin.py); ``rebate_at_hit``
 is refused there as the FD class refuses it.  Voluntary exercise happens on
-the steps flagged EXERCISE only (Bermudan); maturity always exercises.  No
-cash dividends.
+the steps flagged EXERCISE only (Bermudan); maturity always exercises.
+
+Cash dividends are opt-in (``cash_dividends="path"``; the default "refuse"
+refuses them).  A step may then pay a dividend D after its move and before its
+events, through the invertible map g(s) = s - D (s >= 2 D), s / 2 (below) of
+include/fdcn.h; the planner orders the events of a dividend date as the FD
+classes do.
 
 The estimator is the out-of-sample one: a sub-run of 4 096 paths fits a
 cubic in the standardised log-spot per exercise date on one path set and
@@ -51,6 +56,9 @@ _LOWER = ("down-and-out", "double-out", "down-and-in", "double-in")
 _UPPER = ("up-and-out", "double-out", "up-and-in", "double-in")
 _MERGE = 1e-12  # times closer than this are one step
 _THREADS = 256
+_TINY_DIFF = 1e-300  # DIFF of a zero-length step: x absorbs the move
+_LN2 = 0.6931471805599453  # include/fdcn.h
+_CASH_DIVIDENDS = ("refuse", "path")
 
 
 @dataclass
@@ -62,10 +70,24 @@ class LsmContract:
     times: np.ndarray    # [n_steps] t_m
     barrier_type: str
     fixed_price: Optional[float] = None  # answered without a launch (contract_from_pricer)
+    div: Optional[np.ndarray] = None     # [n_steps] cash dividend per step (None: none)
 
     @property
     def n_steps(self) -> int:
         return self.step.shape[0]
+
+    @property
+    def has_dividends(self) -> bool:
+        """An all-zero `div` takes the entry without dividends."""
+        return self.div is not None and bool(np.any(np.asarray(self.div) != 0.0))
+
+    def div_row(self) -> np.ndarray:
+        if self.div is None:
+            return np.zeros(self.n_steps)
+        d = np.asarray(self.div, dtype=float)
+        if d.shape != (self.n_steps,):
+            raise ValueError("LsmContract.div must be shaped [n_steps]")
+        return d
 
 
 @dataclass(frozen=True)
@@ -75,10 +97,13 @@ class LsmConfig:
     seed: int = 42
 
 
-def _step_grid(T: float, exercise: Sequence[float], monitor: Sequence[float]):
+def _step_grid(T: float, exercise: Sequence[float], monitor: Sequence[float],
+               other: Sequence[float] = ()):
     """Sorted union of the exercise and monitor times in (0, T] and T itself,
-    times within _MERGE of each other merged (into T at the end); the flags."""
+    times within _MERGE of each other merged (into T at the end); the flags.
+    `other` times (dividend dates) become steps without a flag."""
     marks = [(float(t), 0) for t in exercise] + [(float(t), 1) for t in monitor] + [(T, 2)]
+    marks += [(float(t), 3) for t in other]
     marks = sorted((T if abs(t - T) <= _MERGE else t, w) for t, w in marks
                    if 0.0 < t <= T + _MERGE)
     times: List[float] = []
@@ -99,12 +124,26 @@ def plan_american_contract(*, spot: float, strike: float, vol: float, option_typ
                            monitor_times: Sequence[float] = (), rebate_amount: float = 0.0,
                            rebate_at_hit: bool = False, n_exercise: int = 64,
                            exercise_times: Optional[Sequence[float]] = None,
-                           dividends: Sequence = ()) -> LsmContract:
+                           dividends: Sequence = (),
+                           cash_dividends: str = "refuse") -> LsmContract:
     """Everything the engines need for one contract: the checks, the step grid
     (the sorted union of k T / n_exercise, or `exercise_times`, and the
     monitor times in (0, T]) and the per-step table.  Rates are continuously
-    compounded; times are year fractions from valuation."""
-    if len(dividends):
+    compounded; times are year fractions from valuation.
+
+    `dividends`, pairs (time, cash), are refused unless cash_dividends="path".
+    Then those inside (0, T) join the step grid (the others are dropped, as the
+    FD pricers drop them), same-date amounts added.  With exercise dates of the
+    American kind (k T / n_exercise, n_exercise > 0) a dividend date t_d is two
+    steps: the first ends at t_d with an EXERCISE flag and no MONITOR flag --
+    the exercise on the cum-dividend spot --, the second has zero length
+    (DRIFT 0, DIFF 1e-300, DF_STEP 1), pays the dividend and carries the
+    date's MONITOR flag and a second EXERCISE flag, both on the ex-dividend
+    spot.  With `exercise_times` (Bermudan) or n_exercise = 0 it is one step:
+    the dividend first, then the date's own events on the ex-dividend spot; a
+    date that is neither an exercise nor a monitoring date is a step without a
+    flag.  CENTRE is rolled through the dividend map, ISCALE is not."""
+    if _check_cash_dividends(cash_dividends) == "refuse" and len(dividends):
         raise ValueError("cash dividends are not supported by the least-squares Monte Carlo.")
     if not (spot > 0.0 and strike > 0.0):
         raise ValueError("spot and strike must be positive.")
@@ -127,58 +166,95 @@ def plan_american_contract(*, spot: float, strike: float, vol: float, option_typ
         raise ValueError(f"{bt} needs a positive upper_barrier.")
     if bt in _LOWER and bt in _UPPER and not lower_barrier < upper_barrier:
         raise ValueError("lower_barrier must be below upper_barrier.")
+    american = False  # a dividend date is exercised cum- and ex-dividend
     if exercise_times is None:
         n_ex = int(n_exercise)
         if n_ex < 0:
             raise ValueError("n_exercise must be >= 0.")
         exercise_times = [k * T / n_ex for k in range(1, n_ex + 1)]
-    times, fl = _step_grid(T, exercise_times, monitor_times if bt != "none" else ())
-    M = times.shape[0]
+        american = n_ex > 0
+    cash: List[tuple] = []
+    for t_d, amount in dividends:
+        t_d, amount = float(t_d), float(amount)
+        if not (math.isfinite(amount) and amount >= 0.0):
+            raise ValueError("a cash dividend must be finite and >= 0.")
+        if amount > 0.0 and 0.0 < t_d < T - _MERGE:
+            cash.append((t_d, amount))
+    if sum(a for _, a in cash) >= spot:
+        raise ValueError("the cash dividends inside the life sum to the spot or more.")
+    times, fl = _step_grid(T, exercise_times, monitor_times if bt != "none" else (),
+                           [t_d for t_d, _ in cash])
+    paid = np.zeros(times.shape[0])
+    for t_d, amount in cash:
+        paid[int(np.argmin(np.abs(times - t_d)))] += amount
+    # rows (t, zero-length, exercise, monitor, dividend)
+    rows: List[tuple] = []
+    for m in range(times.shape[0]):
+        t, ex, mon, d = float(times[m]), bool(fl[m, 0]), bool(fl[m, 1]), float(paid[m])
+        if american and d > 0.0:
+            rows.append((t, False, True, False, 0.0))
+            rows.append((t, True, True, mon, d))
+        else:
+            rows.append((t, False, ex, mon, d))
+    M = len(rows)
     if M > capi.LSM_MAX_STEPS:
         raise ValueError(f"{M} steps: the least-squares Monte Carlo takes at most "
                          f"{capi.LSM_MAX_STEPS}.")
     r, q = float(discount_rate), float(carry_rate)
     S = np.zeros((M, capi.LSM_NSTEP))
-    x0 = math.log(spot)
+    div = np.zeros(M)
+    base = math.log(spot)  # the centre after the last dividend
     prev, sum_drift, sum_var = 0.0, 0.0, 0.0
-    for m in range(M):
-        t = float(times[m])
-        dt = t - prev
-        drift = (q - 0.5 * vol * vol) * dt
-        diff = vol * math.sqrt(dt)
+    for m, (t, zero, ex, mon, d) in enumerate(rows):
+        if zero:
+            drift, diff, df_step = 0.0, _TINY_DIFF, 1.0
+        else:
+            dt = t - prev
+            drift = (q - 0.5 * vol * vol) * dt
+            diff = vol * math.sqrt(dt)
+            df_step = math.exp(-r * dt)
         sum_drift += drift
         sum_var += diff * diff
         S[m, capi.LSM_S_DRIFT] = drift
         S[m, capi.LSM_S_DIFF] = diff
-        S[m, capi.LSM_S_DF_STEP] = math.exp(-r * dt)
+        S[m, capi.LSM_S_DF_STEP] = df_step
         S[m, capi.LSM_S_DF_END] = math.exp(-r * t)
-        S[m, capi.LSM_S_EXERCISE] = 1.0 if fl[m, 0] else 0.0
-        S[m, capi.LSM_S_MONITOR] = 1.0 if fl[m, 1] else 0.0
+        S[m, capi.LSM_S_EXERCISE] = 1.0 if ex else 0.0
+        S[m, capi.LSM_S_MONITOR] = 1.0 if mon else 0.0
         if bt != "none":
             S[m, capi.LSM_S_REBATE] = rebate_value(float(rebate_amount),
                                                    bool(rebate_at_hit) and bt in _KO, q, T - t)
-        S[m, capi.LSM_S_CENTRE] = x0 + sum_drift
+        if d > 0.0:  # the centre goes through the dividend map like a path
+            div[m] = d
+            base = float(_div_forward(np.float64(base + sum_drift), d))
+            sum_drift = 0.0
+        S[m, capi.LSM_S_CENTRE] = base + sum_drift
         S[m, capi.LSM_S_ISCALE] = 1.0 / math.sqrt(sum_var)
         prev = t
     params = np.array([spot, strike, lower_barrier if bt in _LOWER else 0.0,
                        upper_barrier if bt in _UPPER else 0.0], dtype=float)
     flags = np.array([option_type == "put", capi.LSM_KIND[bt], 0], dtype=np.int32)
-    return LsmContract(params=params, flags=flags, step=S, times=times, barrier_type=bt)
+    return LsmContract(params=params, flags=flags, step=S,
+                       times=np.array([row[0] for row in rows]), barrier_type=bt,
+                       div=div if cash_dividends == "path" else None)
 
 
-def contract_from_pricer(p, n_exercise: int = 64) -> LsmContract:
+def contract_from_pricer(p, n_exercise: int = 64, cash_dividends: str = "refuse") -> LsmContract:
     """The contract an AmericanFDMPricer, AmericanBarrierFDMPricer or
     AmericanKnockInFDMPricer prices: its snapped spot and strike (the FD price
     is the price at those), sigma, the continuously compounded discount and
     carry rates, the barrier keywords and the monitoring times of
-    `_monitor_taus`.  A pricer with a dividend in (valuation, maturity] is
-    refused.  An `already_hit` pricer, and a knock-in that can never knock in,
+    `_monitor_taus`.  A pricer with a dividend in (valuation, maturity) is
+    refused, unless cash_dividends="path": then the dividends of
+    `_div_times_tau` go on the path (plan_american_contract).  An
+    `already_hit` pricer, and a knock-in that can never knock in,
     carry the pricer's own answer in `fixed_price` and are never launched; an
     `already_in` pricer is the vanilla contract.  A BermudanFDMPricer
     (bermudan.py) gives its own exercise dates as `exercise_times`
     (`n_exercise` is ignored); one with a monitoring date inside the life that
     is not an exercise date is refused."""
-    if p._div_times_tau():
+    divs = p._div_times_tau()
+    if _check_cash_dividends(cash_dividends) == "refuse" and divs:
         raise ValueError("cash dividends are not supported by the least-squares Monte Carlo.")
     if p.spot_snapped is None and p.strike_snapped is None:
         p._build_log_grid()
@@ -212,7 +288,8 @@ def contract_from_pricer(p, n_exercise: int = 64) -> LsmContract:
         upper_barrier=getattr(p, "upper_barrier", None) if bt in _UPPER else None,
         monitor_times=mon, rebate_amount=getattr(p, "rebate_amount", 0.0),
         rebate_at_hit=getattr(p, "rebate_at_hit", False) and bt in _KO, n_exercise=n_exercise,
-        exercise_times=exercise)
+        exercise_times=exercise, dividends=[(T - tau, cash) for tau, cash in divs],
+        cash_dividends=cash_dividends)
     c.fixed_price = fixed
     return c
 
@@ -233,6 +310,26 @@ def _path_normals(n_steps: int, seed: int, word: int, obs_first: int, antithetic
     p = np.arange(capi.LSM_SUBRUN)
     k, tid = p // _THREADS, p % _THREADS
     return z[(k // 2) * _THREADS + tid] * np.where(k % 2 == 1, -1.0, 1.0)[:, None]
+
+
+def _check_cash_dividends(mode) -> str:
+    if mode not in _CASH_DIVIDENDS:
+        raise ValueError(f"cash_dividends must be 'refuse' or 'path', not {mode!r}")
+    return mode
+
+
+def _div_forward(x: np.ndarray, d: float) -> np.ndarray:
+    """The dividend map g on the log-spot (include/fdcn.h), the kernel's
+    operations."""
+    s = np.exp(x)
+    with np.errstate(all="ignore"):
+        return np.where(s >= 2.0 * d, np.log(s - d), x - _LN2)
+
+
+def _div_backward(x: np.ndarray, d: float) -> np.ndarray:
+    """g's inverse on the log-spot."""
+    s = np.exp(x)
+    return np.where(s >= d, np.log(s + d), x + _LN2)
 
 
 def _cholesky_cubic(sm: np.ndarray):
@@ -313,6 +410,7 @@ def host_subruns(c: LsmContract, subruns: Sequence[int], antithetic: bool, seed:
     exr[M - 1] = False  # maturity is not a fitted step
     reb, dfs, dfe = S[:, capi.LSM_S_REBATE], S[:, capi.LSM_S_DF_STEP], S[:, capi.LSM_S_DF_END]
     centre, iscale = S[:, capi.LSM_S_CENTRE], S[:, capi.LSM_S_ISCALE]
+    D = c.div_row()  # after the move, before the step's events; undone first going back
 
     # ---- A: fit set forward
     Z = normals(2 * int(stream_id))
@@ -321,6 +419,8 @@ def host_subruns(c: LsmContract, subruns: Sequence[int], antithetic: bool, seed:
     for m in range(1, M + 1):
         i = m - 1
         x = x + (drift[i] + diff[i] * Z[:, :, i])
+        if D[i] != 0.0:
+            x = _div_forward(x, D[i])
         if mon[i]:
             h = np.where(breach(np.exp(x)) & (h > M), m, h)
 
@@ -364,6 +464,8 @@ def host_subruns(c: LsmContract, subruns: Sequence[int], antithetic: bool, seed:
                 coef[:, i, 4] = valid
                 if want_fit:
                     fit_u[:, i, :] = np.where(take, u, np.nan)
+        if D[i] != 0.0:
+            x = _div_backward(x, D[i])
         x = x - (drift[i] + diff[i] * Z[:, :, i])
         cf = cf * dfs[i]
     fit_mean = np.sum(cf, axis=1) / float(n)
@@ -377,6 +479,8 @@ def host_subruns(c: LsmContract, subruns: Sequence[int], antithetic: bool, seed:
     for m in range(1, M + 1):
         i = m - 1
         x = x + (drift[i] + diff[i] * Z[:, :, i])
+        if D[i] != 0.0:
+            x = _div_forward(x, D[i])
         fitted = (coef[:, i, 4] != 0.0)[:, None] & bool(exr[i])
         if not (mon[i] or m == M or fitted.any()):
             continue
@@ -485,9 +589,13 @@ def simulate_lsm(group: Sequence[LsmContract], n_subruns: int, antithetic: bool,
     if engine == "hip":
         capi.require_device()
         P, F, S = _stack(group, ids)
+        # one contract with a dividend sends the launch through the div entry
+        div = (np.stack([c.div_row() for c in group]) if any(c.has_dividends for c in group)
+               else None)
         stats, val, coef = capi.mc_lsm_batch(P, F, S, G, antithetic, seed=seed,
                                              obs_first=first * obs_per_subrun(antithetic),
-                                             want_values=want_values, want_coef=want_coef)
+                                             want_values=want_values, want_coef=want_coef,
+                                             div=div)
         out = {"stats": stats}
         if want_values:
             out["values"] = val
@@ -547,15 +655,21 @@ def _result(c: LsmContract, cfg: LsmConfig, G: int, st: Optional[np.ndarray]) ->
 
 def mc_american_batch(contracts: Sequence, cfg: LsmConfig = LsmConfig(), *, engine: str = "hip",
                       stream_ids: Optional[Sequence[int]] = None,
-                      subrun_range: Optional[range] = None) -> List[dict]:
-    """Price many contracts, one launch per distinct step count.  `contracts`:
-    LsmContract objects, or the keyword arguments of plan_american_contract per
-    contract; cfg is shared.  The Philox stream id of a contract is its index
-    in `contracts`, or stream_ids[index].  `subrun_range` (a contiguous range
+                      subrun_range: Optional[range] = None,
+                      cash_dividends: str = "refuse") -> List[dict]:
+    """Price many contracts, one launch per distinct (step count, has
+    dividends).  `contracts`: LsmContract objects, or the keyword arguments of
+    plan_american_contract per contract (planned with `cash_dividends` unless
+    they name their own; an LsmContract that carries dividends was planned with
+    "path" and is priced as it is); cfg is shared.  The Philox stream id of a
+    contract is its index in `contracts`, or stream_ids[index].  `subrun_range` (a contiguous range
     within [0, cfg.n_subruns)) runs that part of every contract's sub-runs only
     -- a rank's shard -- and merge_lsm_stats combines the parts.  Results, in
     input order: price_american_mc's dict plus "sum_mean" and "sum_mean2"."""
-    plans = [c if isinstance(c, LsmContract) else plan_american_contract(**c) for c in contracts]
+    _check_cash_dividends(cash_dividends)
+    plans = [c if isinstance(c, LsmContract)
+             else plan_american_contract(**{"cash_dividends": cash_dividends, **c})
+             for c in contracts]
     lo, hi = 0, int(cfg.n_subruns)
     if hi < 1:
         raise ValueError("cfg.n_subruns must be positive.")
@@ -568,12 +682,12 @@ def mc_american_batch(contracts: Sequence, cfg: LsmConfig = LsmConfig(), *, engi
     if len(ids) != len(plans):
         raise ValueError("one stream id per contract")
     out: List[Optional[dict]] = [None] * len(plans)
-    by_steps: Dict[int, List[int]] = {}
+    by_steps: Dict[tuple, List[int]] = {}
     for k, c in enumerate(plans):
         if c.fixed_price is not None:
             out[k] = _result(c, cfg, hi - lo, None)
         else:
-            by_steps.setdefault(c.n_steps, []).append(k)
+            by_steps.setdefault((c.n_steps, c.has_dividends), []).append(k)
     for members in by_steps.values():
         r = simulate_lsm([plans[k] for k in members], hi - lo, cfg.antithetic, engine=engine,
                          seed=cfg.seed, stream_ids=[ids[k] for k in members], subrun_first=lo)
@@ -584,14 +698,17 @@ def mc_american_batch(contracts: Sequence, cfg: LsmConfig = LsmConfig(), *, engi
 
 def price_american_mc(contract: Optional[LsmContract] = None, *, n_subruns: int = 32,
                       antithetic: bool = True, seed: int = 42, stream_id: int = 0,
-                      engine: str = "hip", **plan_kw) -> Dict[str, object]:
+                      engine: str = "hip", cash_dividends: str = "refuse",
+                      **plan_kw) -> Dict[str, object]:
     """Least-squares Monte Carlo price of one contract -- an LsmContract
     (contract_from_pricer), or the keyword arguments of plan_american_contract
-    -- on the chosen engine.  Keys: price (the out-of-sample estimate), stderr,
+    (`dividends` needs cash_dividends="path") -- on the chosen engine.  Keys:
+    price (the out-of-sample estimate), stderr,
     ci_95, fit_value and fit_stderr (the in-sample estimate, a diagnostic),
     n_paths, n_subruns, steps, invalid_fit_steps, min_margin, barrier_type."""
+    _check_cash_dividends(cash_dividends)
     if contract is None:
-        contract = plan_american_contract(**plan_kw)
+        contract = plan_american_contract(cash_dividends=cash_dividends, **plan_kw)
     elif plan_kw:
         raise TypeError("give a contract or the keywords of plan_american_contract, not both")
     cfg = LsmConfig(n_subruns=int(n_subruns), antithetic=bool(antithetic), seed=int(seed))

@@ -53,7 +53,8 @@ extern "C" {
  * fdcn_mc_lsm_plan) and the Bermudan exercise event (fdcn_session_exercise,
  * fdcn_session_exercise_regions), and the quasi-Monte Carlo paths
  * (fdcn_mc_qmc_batch, fdcn_mc_qmc_batch_dev, fdcn_mc_qmc_plan; fdcn_qmc_normals
- * in fdcn_diag.h).
+ * in fdcn_diag.h), and the least-squares Monte Carlo with cash dividends on
+ * the path (fdcn_mc_lsm_div_batch, fdcn_mc_lsm_div_batch_dev).
  * 7: the BGK barrier pricer's Monte Carlo entry points (fdcn_mc_bgk_batch,
  * fdcn_mc_bgk_batch_dev, fdcn_mc_bgk_plan) were added after 6.
  * 6: the Monte Carlo discrete-barrier entry points (fdcn_mc_barrier_batch,
@@ -834,6 +835,43 @@ int fdcn_mc_lsm_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithe
 int fdcn_mc_lsm_plan(int32_t n_steps, int32_t G, int32_t antithetic, int32_t* obs_per_subrun,
                      int64_t* ws_bytes_per_contract, int64_t* values_per_contract,
                      int64_t* coef_per_contract);
+
+/* ---- The same with cash dividends on the path.  Everything above holds, and
+ *   div [B][n_steps]   cash dividend D_m >= 0 of step m (0.0: none)
+ * is one more input.  Within step m the order is: the move x += DRIFT_m +
+ * DIFF_m * z_m, then the dividend, then the step's events, all on the
+ * ex-dividend spot: the MONITOR test, the exercise decision, the maturity
+ * payoff and the regressor u.  A dividend on the last step therefore acts
+ * before the maturity payoff.  The dividend map on the spot is
+ *   g(s) = s - D  for s >= 2 D,   s / 2  below:
+ * continuous, strictly increasing, positive and invertible, with the inverse
+ * s + D for s >= D and 2 s below.  On the log-spot, with s = exp(x):
+ *   forward  (phases A and C)  x <- log(s - D) if s >= 2 D, else x - ln 2
+ *   backward (phase B)         x <- log(s + D) if s >= D,   else x + ln 2
+ * each operation rounded separately, ln 2 = 0x1.62e42fefa39efp-1; a step with
+ * D_m == 0.0 applies neither.  Phase B walks the fit set backward without
+ * storing it: going from t_m to t_{m-1} it first undoes step m's dividend with
+ * the inverse map and then subtracts the move.  Because g is continuous at
+ * 2 D, a rounding that takes the other branch on the way back (s within
+ * rounding of D there) moves x by rounding error only; a clamp such as max(s -
+ * D, floor) has no inverse and could not be walked back.  CENTRE_m is the
+ * caller's (mc_american.py rolls it through g), ISCALE_m as above.
+ * The step table's layout, FDCN_LSM_NSTEP and the workspace (fdcn_mc_lsm_plan)
+ * do not change, and a launch with an all-zero div gives the numbers of
+ * fdcn_mc_lsm_batch bit for bit.
+ * Validation adds (before any device call; FDCN_EINVAL): div NULL; and, host
+ * entry only, a dividend that is negative or not finite. */
+int fdcn_mc_lsm_div_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                          const double* params, const int32_t* flags, const double* step,
+                          const double* div, uint64_t seed, int64_t obs_first, double* stats,
+                          double* values_out, double* coef_out);
+/* Device pointers, as fdcn_mc_lsm_batch_dev; the contents of div are not
+ * checked here. */
+int fdcn_mc_lsm_div_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                              const double* params, const int32_t* flags, const double* step,
+                              const double* div, uint64_t seed, int64_t obs_first, double* stats,
+                              double* values_out, double* coef_out, double* workspace,
+                              int64_t workspace_bytes, void* stream);
 
 /* ---- host-side plan helpers (no device) -------------------------------- */
 /* Uniform log grid of the pricers' _build_log_grid

@@ -14,8 +14,13 @@ Yardstick, same process: the NumPy host engine (mc_american.host_subruns, the
 same algorithm on the same streams) on `--host-contracts` contracts x
 `--host-subruns` sub-runs, on threads sized from OMP_NUM_THREADS (1 if unset).
 
+--dividends N puts a cash dividend on N steps of every contract (spread over
+the life, none on the last step) and times the dividend instance of the kernel
+(fdcn_mc_lsm_div_batch_dev) beside the plain launch of the same batch without
+them, in the same process: both medians and their ratio join the JSON line.
+
 Prints one JSON line.  --dump-outputs DIR writes the stats of the last timed
-launch as DIR/mc_lsm_stats.npy.  Without a GPU it fails; there is no fallback.
+plain launch as DIR/mc_lsm_stats.npy.  Without a GPU it fails; there is no fallback.
 """
 from __future__ import annotations
 
@@ -58,7 +63,19 @@ def build_batch(B: int, n_steps: int, seed: int = 1):
     return plans
 
 
-def device_run(plans, G: int, launches: int, warmup: int, seed: int):
+def dividend_rows(plans, n_div: int) -> np.ndarray:
+    """[B, n_steps]: 0.4 % of the spot on n_div steps spread over the life."""
+    B, n_steps = len(plans), plans[0].n_steps
+    if not 0 <= n_div < n_steps:
+        raise SystemExit("--dividends must be in 0 .. steps - 1")
+    rows = np.zeros((B, n_steps))
+    at = [((k + 1) * n_steps) // (n_div + 1) - 1 for k in range(n_div)]
+    for b, c in enumerate(plans):
+        rows[b, at] = 0.004 * float(c.params[0])
+    return rows
+
+
+def device_run(plans, G: int, launches: int, warmup: int, seed: int, div=None):
     import torch
     from finite_difference_amd import capi, mc_american
     capi.require_device()
@@ -66,6 +83,7 @@ def device_run(plans, G: int, launches: int, warmup: int, seed: int):
     B, n_steps = len(plans), plans[0].n_steps
     P, F, S = mc_american._stack(plans, list(range(B)))
     dP, dF, dS = (torch.from_numpy(a).to(dev) for a in (P, F, S))
+    dD = torch.from_numpy(np.ascontiguousarray(div)).to(dev) if div is not None else None
     stats = torch.zeros((B, capi.LSM_NSTAT), dtype=torch.float64, device=dev)
     ws_bytes = capi.mc_lsm_plan(n_steps, G, True)["ws_bytes_per_contract"] * B
     ws = torch.zeros(ws_bytes // 8, dtype=torch.float64, device=dev)
@@ -73,6 +91,11 @@ def device_run(plans, G: int, launches: int, warmup: int, seed: int):
     torch.cuda.synchronize()
 
     def launch():
+        if dD is not None:
+            capi.mc_lsm_div_batch_dev(B, n_steps, G, True, dP.data_ptr(), dF.data_ptr(),
+                                      dS.data_ptr(), dD.data_ptr(), seed, 0, stats.data_ptr(),
+                                      None, None, ws.data_ptr(), ws_bytes, stream.cuda_stream)
+            return
         capi.mc_lsm_batch_dev(B, n_steps, G, True, dP.data_ptr(), dF.data_ptr(), dS.data_ptr(),
                               seed, 0, stats.data_ptr(), None, None, ws.data_ptr(), ws_bytes,
                               stream.cuda_stream)
@@ -121,6 +144,8 @@ def main() -> int:
     ap.add_argument("--host-contracts", type=int, default=7)
     ap.add_argument("--host-subruns", type=int, default=4)
     ap.add_argument("--dump-outputs", default="", metavar="DIR")
+    ap.add_argument("--dividends", type=int, default=0, metavar="N",
+                    help="also time the dividend instance with N dividend steps per contract")
     args = ap.parse_args()
 
     from finite_difference_amd import capi
@@ -144,6 +169,18 @@ def main() -> int:
         "invalid_fit_steps": float(stats[:, capi.LSM_O_INVALID].sum()),
         "price_range": [float(stats[:, 0].min()), float(stats[:, 0].max())],
     }
+    if args.dividends:
+        rows = dividend_rows(plans, args.dividends)
+        dt, dstats, _ = device_run(plans, args.subruns, args.launches, args.warmup, args.seed,
+                                   div=rows)
+        dmed = statistics.median(dt)
+        line["dividends"] = {
+            "steps_with_a_dividend": args.dividends,
+            "launch_seconds": {"median": dmed, "min": min(dt), "max": max(dt)},
+            "plain_launch_seconds_median": med,
+            "ratio_to_plain": dmed / med,
+            "price_range": [float(dstats[:, 0].min()), float(dstats[:, 0].max())],
+        }
     if args.dump_outputs:
         os.makedirs(args.dump_outputs, exist_ok=True)
         np.save(os.path.join(args.dump_outputs, "mc_lsm_stats.npy"), stats)
