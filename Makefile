@@ -44,7 +44,8 @@ HDRS := include/fdcn.h include/fdcn_diag.h $(CSRC)/fdcn_shared.h $(CSRC)/fdcn_se
         $(CSRC)/fdcn_qmc_table.h
 DEV_OBJS := build/obj/fdcn_kernels.o build/obj/fdcn_analytic.o build/obj/fdcn_session.o \
             build/obj/fdcn_vc.o build/obj/fdcn_mc.o build/obj/fdcn_mc_bgk.o \
-            build/obj/fdcn_mc_lsm.o build/obj/fdcn_mc_qmc.o
+            build/obj/fdcn_mc_lsm.o build/obj/fdcn_mc_qmc.o \
+            build/obj/fdcn_mc_dual.o
 SAN_TESTS := tests/test_tau_sequence.py tests/test_capi_symbols.py tests/test_scenario_batch.py \
              tests/test_american_batch.py tests/test_barrier_host.py tests/test_american_host.py
 

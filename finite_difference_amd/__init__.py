@@ -18,4 +18,6 @@ from .american_knockin import AmericanKnockInFDMPricer  # noqa: F401
 from .bermudan import BermudanFDMPricer  # noqa: F401
 from .mc_american import (LsmContract, LsmConfig, plan_american_contract,  # noqa: F401
                           contract_from_pricer, simulate_lsm, price_american_mc,
-                          mc_american_batch, merge_lsm_stats)
+                          mc_american_batch, merge_lsm_stats, DualConfig, simulate_dual,
+                          mc_american_bounds_batch, price_american_mc_bounds,
+                          merge_dual_stats, brackets)

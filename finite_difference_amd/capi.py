@@ -50,6 +50,7 @@ EXPORTED = ("fdcn_cn_batch", "fdcn_it_batch", "fdcn_cn_batch_dev", "fdcn_it_batc
             "fdcn_mc_bgk_batch", "fdcn_mc_bgk_batch_dev", "fdcn_mc_bgk_plan",
             "fdcn_mc_lsm_batch", "fdcn_mc_lsm_batch_dev", "fdcn_mc_lsm_plan",
             "fdcn_mc_lsm_div_batch", "fdcn_mc_lsm_div_batch_dev",
+            "fdcn_mc_lsm_dual_batch", "fdcn_mc_lsm_dual_batch_dev", "fdcn_mc_lsm_dual_plan",
             "fdcn_mc_qmc_batch", "fdcn_mc_qmc_batch_dev", "fdcn_mc_qmc_plan")
 # include/fdcn_diag.h: test / tuning entry points, not the product boundary
 DIAG_EXPORTED = ("fdcn_force_variant", "fdcn_forced_variant", "fdcn_variant_name",
@@ -81,6 +82,10 @@ LSM_F_PUT, LSM_F_KIND, LSM_F_STREAM = range(3)
  LSM_S_REBATE, LSM_S_CENTRE, LSM_S_ISCALE) = range(9)
 (LSM_O_PRICE, LSM_O_STDERR, LSM_O_FIT_VALUE, LSM_O_FIT_STDERR, LSM_O_SUM, LSM_O_SUM2,
  LSM_O_INVALID, LSM_O_MIN_MARGIN) = range(8)
+# its dual upper bound (enum fdcn_dual_stat)
+DUAL_MAX_OUTER, DUAL_MAX_INNER, DUAL_NSTAT = 1024, 16384, 7
+(DUAL_O_GAP, DUAL_O_STDERR, DUAL_O_SUM, DUAL_O_SUM2, DUAL_O_MIN_MARGIN, DUAL_O_INNER_PATHS,
+ DUAL_O_INNER_STEPS) = range(7)
 LSM_KIND = {"none": 0, "down-and-out": 1, "up-and-out": 2, "double-out": 3, "down-and-in": 4,
             "up-and-in": 5, "double-in": 6}
 
@@ -301,6 +306,18 @@ def lib() -> ctypes.CDLL:
             L.fdcn_mc_lsm_plan.argtypes = [_I, _I, _I, _PI, ctypes.POINTER(ctypes.c_int64),
                                            ctypes.POINTER(ctypes.c_int64),
                                            ctypes.POINTER(ctypes.c_int64)]
+            L.fdcn_mc_lsm_dual_batch.restype = _I
+            L.fdcn_mc_lsm_dual_batch.argtypes = [_I, _I, _I, _I, _I, _I, _V, _V, _V, _V,
+                                                 ctypes.c_uint64, _I64, _V, _V, _V]
+            L.fdcn_mc_lsm_dual_batch_dev.restype = _I
+            L.fdcn_mc_lsm_dual_batch_dev.argtypes = [_I, _I, _I, _I, _I, _I, _V, _V, _V, _V,
+                                                     ctypes.c_uint64, _I64, _V, _V, _V, _V, _I64,
+                                                     _V]
+            L.fdcn_mc_lsm_dual_plan.restype = _I
+            L.fdcn_mc_lsm_dual_plan.argtypes = [_I, _I, _I, _I, _I,
+                                                ctypes.POINTER(ctypes.c_int64),
+                                                ctypes.POINTER(ctypes.c_int64),
+                                                ctypes.POINTER(ctypes.c_int64)]
             L.fdcn_mc_normals.restype = _I
             L.fdcn_mc_normals.argtypes = [_I64, _I, ctypes.c_uint64, _I, _I64, _V]
             L.fdcn_mc_qmc_batch.restype = _I
@@ -968,3 +985,59 @@ def mc_lsm_div_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, params_
         int(B), int(n_steps), int(G), 1 if antithetic else 0, params_ptr, flags_ptr, step_ptr,
         div_ptr, int(seed) & (2 ** 64 - 1), int(obs_first), stats_ptr, values_ptr, coef_ptr,
         workspace_ptr, int(workspace_bytes), stream_ptr))
+
+
+def mc_dual_plan(n_steps: int, G: int, antithetic: bool, n_outer: int, n_inner: int) -> dict:
+    """Geometry of a dual-bound launch (fdcn_mc_lsm_dual_plan; host only):
+    workspace bytes per contract, doubles per contract of the gap dump and of
+    the continuation-value dump."""
+    ws, ng, nc = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    _check(lib().fdcn_mc_lsm_dual_plan(int(n_steps), int(G), 1 if antithetic else 0, int(n_outer),
+                                       int(n_inner), ctypes.byref(ws), ctypes.byref(ng),
+                                       ctypes.byref(nc)))
+    return dict(ws_bytes_per_contract=ws.value, gap_per_contract=ng.value,
+                cont_per_contract=nc.value)
+
+
+def mc_dual_batch(params, flags, step, coef, n_outer: int, n_inner: int, antithetic: bool, *,
+                  seed: int = 0, subrun_first: int = 0, want_gap: bool = False,
+                  want_cont: bool = False):
+    """fdcn_mc_lsm_dual_batch on host arrays -> (stats [B, DUAL_NSTAT], gap
+    [B, G * n_outer] or None, cont [B, G * n_outer, n_steps] or None).  params
+    [B, LSM_NPARAM], flags [B, LSM_NFLAG], step [B, n_steps, LSM_NSTEP], coef
+    [B, G, n_steps, LSM_NCOEF] (mc_lsm_batch's coefficient dump)."""
+    require_device()
+    P = _f64(params).reshape(-1, LSM_NPARAM)
+    F = _i32(flags).reshape(-1, LSM_NFLAG)
+    S = _f64(step)
+    C = _f64(coef)
+    B = P.shape[0]
+    if F.shape[0] != B or S.ndim != 3 or S.shape[0] != B or S.shape[2] != LSM_NSTEP:
+        raise ValueError("mc_dual_batch: params [B, 4], flags [B, 3], step [B, n_steps, 9]")
+    n_steps = S.shape[1]
+    if C.ndim != 4 or C.shape[0] != B or C.shape[2:] != (n_steps, LSM_NCOEF) or C.shape[1] < 1:
+        raise ValueError("mc_dual_batch: coef [B, G, n_steps, 5]")
+    G, n_outer = C.shape[1], int(n_outer)
+    stats = np.empty((B, DUAL_NSTAT), dtype=np.float64)
+    rows = G * max(n_outer, 0)
+    gap = np.empty((B, rows), dtype=np.float64) if want_gap else None
+    cont = np.empty((B, rows, n_steps), dtype=np.float64) if want_cont else None
+    _check(lib().fdcn_mc_lsm_dual_batch(
+        B, n_steps, G, 1 if antithetic else 0, n_outer, int(n_inner), P.ctypes.data,
+        F.ctypes.data, S.ctypes.data, C.ctypes.data, int(seed) & (2 ** 64 - 1),
+        int(subrun_first), stats.ctypes.data, gap.ctypes.data if want_gap else None,
+        cont.ctypes.data if want_cont else None))
+    return stats, gap, cont
+
+
+def mc_dual_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, n_outer: int, n_inner: int,
+                      params_ptr: int, flags_ptr: int, step_ptr: int, coef_ptr: int, seed: int,
+                      subrun_first: int, stats_ptr: int, gap_ptr: Optional[int],
+                      cont_ptr: Optional[int], workspace_ptr: Optional[int],
+                      workspace_bytes: int, stream_ptr: Optional[int]) -> None:
+    """fdcn_mc_lsm_dual_batch_dev: every array already on the device;
+    asynchronous on `stream_ptr`."""
+    _check(lib().fdcn_mc_lsm_dual_batch_dev(
+        int(B), int(n_steps), int(G), 1 if antithetic else 0, int(n_outer), int(n_inner),
+        params_ptr, flags_ptr, step_ptr, coef_ptr, int(seed) & (2 ** 64 - 1), int(subrun_first),
+        stats_ptr, gap_ptr, cont_ptr, workspace_ptr, int(workspace_bytes), stream_ptr))

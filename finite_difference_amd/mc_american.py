@@ -33,6 +33,16 @@ the mean of their means and its standard error comes from their spread.
   path on the same Philox streams (include/fdcn.h), so the two agree path for
   path up to exp / log and summation order.
 
+The lower bound has an upper one beside it (``mc_american_bounds_batch``,
+``price_american_mc_bounds``): the Andersen-Broadie dual bound.  The policy a
+sub-run has fitted drives a nested simulation -- outer paths, and at every
+date on which the holder may stop, inner paths that follow the policy from
+there -- which gives a gap >= 0 such that price + gap is an upper bound in
+expectation whatever the policy (include/fdcn.h, fdcn_mc_lsm_dual_batch;
+csrc/fdcn_mc_dual.hip on the device, ``host_dual_subruns`` in NumPy).
+``brackets`` is the comparison of an FD price with the two bounds.  Cash
+dividends are out of scope there: a contract that carries them is refused.
+
 A missing GPU under ``engine="hip"`` is an error, never a silent fallback.
 """
 from __future__ import annotations
@@ -45,10 +55,12 @@ import numpy as np
 
 from . import capi
 from .barrier import rebate_value
-from .mc_barrier import philox_normals
+from .mc_barrier import philox4x32_10, philox_normals
 
 __all__ = ["LsmContract", "LsmConfig", "plan_american_contract", "contract_from_pricer",
-           "simulate_lsm", "price_american_mc", "mc_american_batch", "merge_lsm_stats"]
+           "simulate_lsm", "price_american_mc", "mc_american_batch", "merge_lsm_stats",
+           "DualConfig", "host_dual_subruns", "simulate_dual", "mc_american_bounds_batch",
+           "price_american_mc_bounds", "merge_dual_stats", "brackets"]
 
 _KO = ("down-and-out", "up-and-out", "double-out")
 _KI = ("down-and-in", "up-and-in", "double-in")
@@ -716,3 +728,439 @@ def price_american_mc(contract: Optional[LsmContract] = None, *, n_subruns: int 
     res.pop("sum_mean")
     res.pop("sum_mean2")
     return res
+
+
+# ---------------------------------------------------------------------------
+# the dual upper bound (include/fdcn.h, fdcn_mc_lsm_dual_batch)
+# ---------------------------------------------------------------------------
+_DUAL_BIT = 1 << 31              # bit 31 of counter word 3: the dual's streams
+_OBS_BITS, _STEP_BITS, _OUTER_BITS = 14, 9, 10  # fields of the inner observation index
+_INNER_CHUNK = 1 << 22           # path-steps of normals held at once by the host engine
+
+
+@dataclass(frozen=True)
+class DualConfig:
+    n_outer: int = 8      # outer paths per sub-run
+    n_inner: int = 2048   # inner paths per start
+
+
+def _normals_at(obs: np.ndarray, n_steps: int, seed: int, word: int) -> np.ndarray:
+    """z [..., n_steps] of the observations `obs` (uint64, any shape): the
+    mapping of philox_normals for observation numbers that are not a range."""
+    n_pairs = (n_steps + 1) // 2
+    obs = np.asarray(obs, dtype=np.uint64)
+    ctr = np.empty(obs.shape + (n_pairs, 4), dtype=np.uint64)
+    ctr[..., 0] = (obs & np.uint64(0xFFFFFFFF))[..., None]
+    ctr[..., 1] = (obs >> np.uint64(32))[..., None]
+    ctr[..., 2] = np.arange(n_pairs, dtype=np.uint64)
+    ctr[..., 3] = np.uint64(int(word))
+    seed = int(seed) & (2 ** 64 - 1)
+    w = philox4x32_10(ctr, (seed & 0xFFFFFFFF, seed >> 32))
+
+    def u53(hi, lo):
+        return ((hi >> np.uint32(5)).astype(np.float64) * 67108864.0
+                + (lo >> np.uint32(6)).astype(np.float64) + 0.5) * 2.0 ** -53
+    u1, u2 = u53(w[..., 0], w[..., 1]), u53(w[..., 2], w[..., 3])
+    r = np.sqrt(-2.0 * np.log(u1))
+    z = np.empty(obs.shape + (2 * n_pairs,))
+    z[..., 0::2] = r * np.cos(2.0 * np.pi * u2)
+    z[..., 1::2] = r * np.sin(2.0 * np.pi * u2)
+    return z[..., :n_steps]
+
+
+def _block_sum(v: np.ndarray) -> np.ndarray:
+    """The kernel's sum of v [rows, n_inner] (path order): each thread its
+    slots in slot order, then the fixed tree over the 256 threads."""
+    rows = v.shape[0]
+    v = v.reshape(rows, -1, _THREADS)
+    s = np.zeros((rows, _THREADS))
+    for k in range(v.shape[1]):
+        s = s + v[:, k, :]
+    off = _THREADS // 2
+    while off > 0:
+        s = s[:, :off] + s[:, off:2 * off]
+        off //= 2
+    return s[:, 0]
+
+
+def _check_dual_sizes(n_outer, n_inner, antithetic: bool) -> None:
+    if int(n_outer) != n_outer or not 1 <= n_outer <= capi.DUAL_MAX_OUTER:
+        raise ValueError(f"n_outer must be in 1 .. {capi.DUAL_MAX_OUTER}")
+    unit = 2 * _THREADS if antithetic else _THREADS
+    if int(n_inner) != n_inner or not unit <= n_inner <= capi.DUAL_MAX_INNER or n_inner % unit:
+        raise ValueError(f"n_inner must be a multiple of {_THREADS} ({2 * _THREADS} when "
+                         f"antithetic) up to {capi.DUAL_MAX_INNER}")
+
+
+def _check_dual_contract(c: LsmContract) -> None:
+    if c.has_dividends:
+        raise ValueError("cash dividends are out of the dual bound's scope.")
+    if int(c.flags[capi.LSM_F_KIND]) != 0 and np.any(c.step[:, capi.LSM_S_REBATE] < 0.0):
+        raise ValueError("a negative rebate: the dual bound needs every cashflow >= 0.")
+
+
+def host_dual_subruns(c: LsmContract, coef: np.ndarray, subruns: Sequence[int], n_outer: int,
+                      n_inner: int, antithetic: bool, seed: int, stream_id: int) -> dict:
+    """The dual estimator for the sub-runs `subruns` (absolute numbers) of
+    contract c under the policies coef [g, n_steps, LSM_NCOEF], row for row of
+    `subruns`: the kernel's operations per path on the same streams, the g *
+    n_outer outer paths side by side.  -> gaps [g, n_outer] (D per outer
+    path), cont [g, n_outer, n_steps] (the inner means, 0.0 where none was
+    run), margin [g], inner_paths [g], inner_steps [g]."""
+    _check_dual_sizes(n_outer, n_inner, bool(antithetic))
+    _check_dual_contract(c)
+    P, F, S = c.params, c.flags, c.step
+    M, ng = c.n_steps, len(subruns)
+    coef = np.asarray(coef, dtype=float)
+    if coef.shape != (ng, M, capi.LSM_NCOEF):
+        raise ValueError("host_dual_subruns: coef [len(subruns), n_steps, LSM_NCOEF]")
+    if any(not 0 <= int(g) < 2 ** 31 for g in subruns):
+        raise ValueError("host_dual_subruns: sub-run numbers must be in 0 .. 2^31 - 1")
+    strike, lower, upper = float(P[capi.LSM_P_STRIKE]), float(P[capi.LSM_P_LOWER]), \
+        float(P[capi.LSM_P_UPPER])
+    put, kind = bool(F[capi.LSM_F_PUT]), int(F[capi.LSM_F_KIND])
+    ko, ki = 1 <= kind <= 3, kind >= 4
+    has_lo, has_hi = kind in (1, 3, 4, 6), kind in (2, 3, 5, 6)
+    x0 = float(np.log(P[capi.LSM_P_SPOT]))
+    w_outer = _DUAL_BIT + 2 * int(stream_id)
+    w_inner = w_outer + 1
+    n_obs = n_inner // 2 if antithetic else n_inner
+    # inner path i of a start: its observation and the sign of its z
+    i_path = np.arange(n_inner)
+    k_slot, tid = i_path // _THREADS, i_path % _THREADS
+    if antithetic:
+        obs_of, sign = (k_slot // 2) * _THREADS + tid, np.where(k_slot % 2 == 1, -1.0, 1.0)
+    else:
+        obs_of, sign = i_path, np.ones(n_inner)
+
+    def payoff(s):
+        return np.maximum(strike - s, 0.0) if put else np.maximum(s - strike, 0.0)
+
+    def breach(s):
+        out = np.zeros(s.shape, dtype=bool)
+        if has_lo:
+            out |= s <= lower
+        if has_hi:
+            out |= s >= upper
+        return out
+
+    drift, diff = S[:, capi.LSM_S_DRIFT], S[:, capi.LSM_S_DIFF]
+    mon = (S[:, capi.LSM_S_MONITOR] != 0.0) & (kind != 0)
+    exr = S[:, capi.LSM_S_EXERCISE] != 0.0
+    exr[M - 1] = False
+    reb, dfe = S[:, capi.LSM_S_REBATE], S[:, capi.LSM_S_DF_END]
+    centre, iscale = S[:, capi.LSM_S_CENTRE], S[:, capi.LSM_S_ISCALE]
+
+    R = ng * n_outer                                   # outer paths, row = g * n_outer + p
+    sub = np.repeat(np.asarray([int(g) for g in subruns], dtype=np.uint64), n_outer)
+    pth = np.tile(np.arange(n_outer, dtype=np.uint64), ng)
+    crow = np.repeat(np.arange(ng), n_outer)           # coefficient row of an outer path
+    Zo = _normals_at(sub * np.uint64(n_outer) + pth, M, seed, w_outer)
+    margin = np.full(R, np.inf)
+    walked = np.zeros(R)
+    starts = np.zeros(R)
+    cont = np.zeros((R, M))
+
+    def inner(rows, i, x_start, in_start):
+        """The mean over n_inner paths from step i + 1 (0-based i: the start
+        step m = i + 1) for the outer paths `rows`."""
+        n_rem = M - (i + 1)
+        base = ((((sub[rows] << np.uint64(_OUTER_BITS)) + pth[rows]) << np.uint64(_STEP_BITS))
+                + np.uint64(i)) << np.uint64(_OBS_BITS)
+        z = _normals_at(base[:, None] + np.arange(n_obs, dtype=np.uint64)[None, :], n_rem, seed,
+                        w_inner)
+        n = len(rows)
+        cr = coef[crow[rows]]                          # [n, M, NCOEF]
+        x = np.repeat(x_start[:, None], n_inner, axis=1)
+        inn = np.repeat(in_start[:, None], n_inner, axis=1)
+        val = np.zeros((n, n_inner))
+        done = np.zeros((n, n_inner), dtype=bool)
+        for t in range(n_rem):
+            if done.all():
+                break
+            ii = i + 1 + t
+            walked[rows] += np.sum(~done, axis=1)
+            x = x + (drift[ii] + diff[ii] * (z[:, obs_of, t] * sign[None, :]))
+            fitted = (cr[:, ii, 4] != 0.0)[:, None] & bool(exr[ii])
+            if not (mon[ii] or ii == M - 1 or fitted.any()):
+                continue
+            s = np.exp(x)
+            phi = payoff(s)
+            hit = breach(s) if mon[ii] else np.zeros((n, n_inner), dtype=bool)
+            if ko:
+                k = hit & ~done
+                val = np.where(k, np.maximum(phi, reb[ii]) * dfe[ii], val)
+                done |= k
+            if ki:
+                inn = inn | (hit & ~done)
+            elig = inn if ki else np.ones((n, n_inner), dtype=bool)
+            if ii == M - 1:
+                val = np.where(~done, np.where(elig, phi, reb[ii]) * dfe[ii], val)
+                done[:] = True
+            else:
+                cand = ~done & fitted & elig & (phi > 0.0)
+                if cand.any():
+                    u = (x - centre[ii]) * iscale[ii]
+                    fit = _cubic(cr[:, ii, :4], u)
+                    gap = np.where(cand, np.abs(phi - fit), np.inf)
+                    margin[rows] = np.minimum(margin[rows], gap.min(axis=1))
+                    go = cand & (phi > fit)
+                    val = np.where(go, phi * dfe[ii], val)
+                    done |= go
+        return _block_sum(val) / float(n_inner)
+
+    x = np.full(R, x0)
+    r = np.zeros(R)
+    D = np.full(R, -np.inf)
+    inn = np.zeros(R, dtype=bool)
+    alive = np.ones(R, dtype=bool)
+    for i in range(M):
+        x = x + (drift[i] + diff[i] * Zo[:, i])
+        last = i == M - 1
+        if not (mon[i] or exr[i] or last):
+            continue
+        s = np.exp(x)
+        phi = payoff(s)
+        hit = breach(s) if mon[i] else np.zeros(R, dtype=bool)
+        forced = alive & ((hit & ko) | last)
+        if ki:
+            inn = inn | (hit & alive)
+        elig = inn if ki else np.ones(R, dtype=bool)
+        start = alive & ~forced & bool(exr[i]) & elig & (phi > 0.0)
+        rows_all = np.nonzero(start)[0]
+        per = max(1, _INNER_CHUNK // max(1, n_inner * (M - 1 - i)))
+        for lo in range(0, len(rows_all), per):
+            rows = rows_all[lo:lo + per]
+            chat = inner(rows, i, x[rows], inn[rows])
+            cont[rows, i] = chat
+            starts[rows] += 1.0
+            cc = coef[crow[rows], i]
+            valid = cc[:, 4] != 0.0
+            u = (x[rows] - centre[i]) * iscale[i]
+            fit = cc[:, 0] + u * (cc[:, 1] + u * (cc[:, 2] + u * cc[:, 3]))
+            margin[rows] = np.where(valid, np.minimum(margin[rows], np.abs(phi[rows] - fit)),
+                                    margin[rows])
+            stops = valid & (phi[rows] > fit)
+            zc = phi[rows] * dfe[i] - chat
+            D[rows] = np.where(stops, np.maximum(D[rows], 0.0 - r[rows]),
+                               np.maximum(D[rows], zc - r[rows]))
+            r[rows] = np.where(stops, r[rows] + zc, r[rows])
+        D = np.where(forced, np.maximum(D, 0.0 - r), D)
+        alive = alive & ~forced
+    return dict(gaps=D.reshape(ng, n_outer), cont=cont.reshape(ng, n_outer, M),
+                margin=margin.reshape(ng, n_outer).min(axis=1),
+                inner_paths=starts.reshape(ng, n_outer).sum(axis=1) * float(n_inner),
+                inner_steps=walked.reshape(ng, n_outer).sum(axis=1))
+
+
+def _finalize_dual(gaps: np.ndarray, margin: float, paths: float, steps: float) -> np.ndarray:
+    """One row of stats [DUAL_NSTAT] from the D of the outer paths, gaps
+    [G, n_outer]: the kernels' sums in their order, _finalize's formulas."""
+    G, n_outer = gaps.shape
+    s, s2 = 0.0, 0.0
+    for g in range(G):
+        tot = 0.0
+        for p in range(n_outer):
+            tot += float(gaps[g, p])
+        gap = tot / float(n_outer)
+        s += gap
+        s2 += gap * gap
+    n = float(G)
+    se = math.sqrt(max(0.0, s2 - s * s / n) / (n - 1.0) / n) if G > 1 else 0.0
+    return np.array([s / n, se, s, s2, float(margin), float(paths), float(steps)])
+
+
+def merge_dual_stats(parts) -> Dict[str, float]:
+    """Gap and standard error of the union of disjoint sub-run ranges of one
+    contract, from their (G, sum, sum of squares) of the sub-run gaps --
+    tuples, or the result dicts of mc_american_bounds_batch (merge_lsm_stats
+    does the lower bound's)."""
+    G, s, s2 = 0, 0.0, 0.0
+    for part in parts:
+        if isinstance(part, dict):
+            part = (part["n_subruns"], part["sum_gap"], part["sum_gap2"])
+        G += int(part[0])
+        s += float(part[1])
+        s2 += float(part[2])
+    if G <= 0:
+        raise ValueError("merge_dual_stats: no sub-runs")
+    n = float(G)
+    stderr = math.sqrt(max(0.0, s2 - s * s / n) / (n - 1.0) / n) if G > 1 else 0.0
+    return {"gap": s / n, "gap_stderr": stderr, "n_subruns": G, "sum_gap": s, "sum_gap2": s2}
+
+
+def simulate_dual(group: Sequence[LsmContract], coef: np.ndarray, n_outer: int, n_inner: int,
+                  antithetic: bool, *, engine: str = "hip", seed: int = 0,
+                  stream_ids: Optional[Sequence[int]] = None, subrun_first: int = 0,
+                  want_gap: bool = False, want_cont: bool = False, host_chunk: int = 16) -> dict:
+    """The dual estimator for contracts that share n_steps, under the policies
+    coef [B, G, n_steps, LSM_NCOEF] -- simulate_lsm's "coef" of sub-runs
+    subrun_first .. subrun_first + G - 1 with the same seed and stream ids.
+    -> {"stats": [B, DUAL_NSTAT]} plus "gap" [B, G * n_outer] and "cont"
+    [B, G * n_outer, n_steps] where asked for."""
+    if engine not in ("hip", "host"):
+        raise ValueError("engine must be 'hip' or 'host'")
+    B = len(group)
+    if B < 1:
+        raise ValueError("simulate_dual: no contracts")
+    n_steps = group[0].n_steps
+    if any(c.n_steps != n_steps for c in group):
+        raise ValueError("simulate_dual: the contracts of a launch share n_steps")
+    if n_steps > capi.LSM_MAX_STEPS:
+        raise ValueError(f"simulate_dual: at most {capi.LSM_MAX_STEPS} steps")
+    if coef is None:
+        raise ValueError("simulate_dual: coef is missing (simulate_lsm with want_coef=True)")
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    if (coef.ndim != 4 or coef.shape[0] != B or coef.shape[1] < 1
+            or coef.shape[2:] != (n_steps, capi.LSM_NCOEF)):
+        raise ValueError("simulate_dual: coef [B, G, n_steps, LSM_NCOEF]")
+    if not np.all(np.isfinite(coef)):
+        raise ValueError("simulate_dual: a coefficient is not finite")
+    G = coef.shape[1]
+    antithetic = bool(antithetic)
+    _check_dual_sizes(n_outer, n_inner, antithetic)
+    n_outer, n_inner = int(n_outer), int(n_inner)
+    first = int(subrun_first)
+    if first != subrun_first or first < 0 or first + G > 2 ** 31:
+        raise ValueError("simulate_dual: subrun_first must be a whole, non-negative number of "
+                         "sub-runs with subrun_first + G <= 2^31")
+    ids = list(range(B)) if stream_ids is None else [int(s) for s in stream_ids]
+    if len(ids) != B:
+        raise ValueError("simulate_dual: one stream id per contract")
+    if any(not 0 <= s < 2 ** 30 for s in ids):
+        raise ValueError("simulate_dual: stream ids must be in 0 .. 2^30 - 1")
+    for c in group:
+        _check_dual_contract(c)
+    if engine == "hip":
+        capi.require_device()
+        P, F, S = _stack(group, ids)
+        stats, gap, cont = capi.mc_dual_batch(P, F, S, coef, n_outer, n_inner, antithetic,
+                                              seed=seed, subrun_first=first, want_gap=want_gap,
+                                              want_cont=want_cont)
+    else:
+        stats = np.empty((B, capi.DUAL_NSTAT))
+        gap = np.empty((B, G * n_outer))
+        cont = np.empty((B, G * n_outer, n_steps)) if want_cont else None
+        step = max(1, int(host_chunk))
+        for b, c in enumerate(group):
+            margin, paths, steps = math.inf, 0.0, 0.0
+            for lo in range(0, G, step):
+                hi = min(G, lo + step)
+                r = host_dual_subruns(c, coef[b, lo:hi], range(first + lo, first + hi), n_outer,
+                                      n_inner, antithetic, seed, ids[b])
+                gap[b, lo * n_outer:hi * n_outer] = r["gaps"].reshape(-1)
+                if want_cont:
+                    cont[b, lo * n_outer:hi * n_outer] = r["cont"].reshape(-1, n_steps)
+                margin = min(margin, float(r["margin"].min()))
+                paths += float(r["inner_paths"].sum())
+                steps += float(r["inner_steps"].sum())
+            stats[b] = _finalize_dual(gap[b].reshape(G, n_outer), margin, paths, steps)
+        if not want_gap:
+            gap = None
+    out = {"stats": stats}
+    if want_gap:
+        out["gap"] = gap
+    if want_cont:
+        out["cont"] = cont
+    return out
+
+
+def _bounds_result(res: dict, dual: DualConfig, st: Optional[np.ndarray]) -> dict:
+    if st is None:  # a fixed price: nothing simulated, both bounds are the price
+        st = np.array([0.0, 0.0, 0.0, 0.0, math.inf, 0.0, 0.0])
+    gap, gap_se = float(st[capi.DUAL_O_GAP]), float(st[capi.DUAL_O_STDERR])
+    res = dict(res)
+    res.update({
+        "gap": gap,
+        "gap_stderr": gap_se,
+        "upper": res["price"] + gap,
+        "upper_stderr": math.sqrt(res["stderr"] ** 2 + gap_se ** 2),
+        "n_outer": int(dual.n_outer),
+        "n_inner": int(dual.n_inner),
+        "sum_gap": float(st[capi.DUAL_O_SUM]),
+        "sum_gap2": float(st[capi.DUAL_O_SUM2]),
+        "dual_min_margin": float(st[capi.DUAL_O_MIN_MARGIN]),
+        "inner_paths": int(st[capi.DUAL_O_INNER_PATHS]),
+    })
+    return res
+
+
+def mc_american_bounds_batch(contracts: Sequence, cfg: LsmConfig = LsmConfig(),
+                             dual: DualConfig = DualConfig(), *, engine: str = "hip",
+                             stream_ids: Optional[Sequence[int]] = None,
+                             subrun_range: Optional[range] = None) -> List[dict]:
+    """Lower and upper bound of many contracts: per distinct step count one
+    least-squares Monte Carlo launch that keeps its coefficients, then one
+    dual launch under them.  Arguments as mc_american_batch (contracts with
+    cash dividends are refused).  Results, in input order: mc_american_batch's
+    dict plus "gap" and "gap_stderr" (mean and standard error of the sub-run
+    gaps), "upper" = price + gap, "upper_stderr" = sqrt(stderr^2 +
+    gap_stderr^2), "n_outer", "n_inner", "sum_gap" and "sum_gap2"
+    (merge_dual_stats), "dual_min_margin" and "inner_paths".
+
+    upper_stderr ignores the covariance between a sub-run's lower mean and its
+    gap.  That covariance is negative -- a sub-run with a poor policy has a low
+    mean and a large gap --, so the figure errs wide.  The inner-sampling noise
+    biases the gap upward by an amount that shrinks with n_inner: the safe
+    side for an upper bound.  A contract with a `fixed_price` gets gap 0 and
+    upper = price."""
+    plans = [c if isinstance(c, LsmContract) else plan_american_contract(**c) for c in contracts]
+    for c in plans:
+        _check_dual_contract(c)
+    _check_dual_sizes(dual.n_outer, dual.n_inner, bool(cfg.antithetic))
+    lo, hi = 0, int(cfg.n_subruns)
+    if hi < 1:
+        raise ValueError("cfg.n_subruns must be positive.")
+    if subrun_range is not None:
+        lo, hi = subrun_range.start, subrun_range.stop
+        if subrun_range.step != 1 or not 0 <= lo < hi <= cfg.n_subruns:
+            raise ValueError("subrun_range must be a non-empty contiguous range within the "
+                             "contract's sub-runs")
+    ids = list(range(len(plans))) if stream_ids is None else [int(s) for s in stream_ids]
+    if len(ids) != len(plans):
+        raise ValueError("one stream id per contract")
+    out: List[Optional[dict]] = [None] * len(plans)
+    by_steps: Dict[int, List[int]] = {}
+    for k, c in enumerate(plans):
+        if c.fixed_price is not None:
+            out[k] = _bounds_result(_result(c, cfg, hi - lo, None), dual, None)
+        else:
+            by_steps.setdefault(c.n_steps, []).append(k)
+    for members in by_steps.values():
+        group = [plans[k] for k in members]
+        kw = dict(engine=engine, seed=cfg.seed, stream_ids=[ids[k] for k in members],
+                  subrun_first=lo)
+        r = simulate_lsm(group, hi - lo, cfg.antithetic, want_coef=True, **kw)
+        d = simulate_dual(group, r["coef"], dual.n_outer, dual.n_inner, cfg.antithetic, **kw)
+        for row, k in enumerate(members):
+            out[k] = _bounds_result(_result(plans[k], cfg, hi - lo, r["stats"][row]), dual,
+                                    d["stats"][row])
+    return out  # type: ignore[return-value]
+
+
+def price_american_mc_bounds(contract: Optional[LsmContract] = None, *, n_subruns: int = 32,
+                             antithetic: bool = True, seed: int = 42, stream_id: int = 0,
+                             n_outer: int = 8, n_inner: int = 2048, engine: str = "hip",
+                             **plan_kw) -> Dict[str, object]:
+    """Lower and upper bound of one contract -- an LsmContract, or the keyword
+    arguments of plan_american_contract: price_american_mc's keys plus those
+    mc_american_bounds_batch adds."""
+    if contract is None:
+        contract = plan_american_contract(**plan_kw)
+    elif plan_kw:
+        raise TypeError("give a contract or the keywords of plan_american_contract, not both")
+    cfg = LsmConfig(n_subruns=int(n_subruns), antithetic=bool(antithetic), seed=int(seed))
+    return mc_american_bounds_batch([contract], cfg, DualConfig(int(n_outer), int(n_inner)),
+                                    engine=engine, stream_ids=[stream_id])[0]
+
+
+def brackets(result: dict, fd_price: float, grid_error: float = 0.0, z: float = 5.0) -> bool:
+    """Does the two-sided bracket of `result` (mc_american_bounds_batch) hold
+    `fd_price`?  True when
+        price - z * stderr - grid_error <= fd_price <= upper + z * upper_stderr + grid_error,
+    grid_error the FD price's own uncertainty (its change over the last grid
+    doubling, say).  No percentage allowance: the lower bound's policy bias is
+    what the upper bound is there for."""
+    lower = float(result["price"]) - z * float(result["stderr"]) - float(grid_error)
+    upper = float(result["upper"]) + z * float(result["upper_stderr"]) + float(grid_error)
+    return bool(lower <= float(fd_price) <= upper)

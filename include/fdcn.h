@@ -54,7 +54,9 @@ extern "C" {
  * fdcn_session_exercise_regions), and the quasi-Monte Carlo paths
  * (fdcn_mc_qmc_batch, fdcn_mc_qmc_batch_dev, fdcn_mc_qmc_plan; fdcn_qmc_normals
  * in fdcn_diag.h), and the least-squares Monte Carlo with cash dividends on
- * the path (fdcn_mc_lsm_div_batch, fdcn_mc_lsm_div_batch_dev).
+ * the path (fdcn_mc_lsm_div_batch, fdcn_mc_lsm_div_batch_dev), and the dual
+ * upper bound of the least-squares Monte Carlo (fdcn_mc_lsm_dual_batch,
+ * fdcn_mc_lsm_dual_batch_dev, fdcn_mc_lsm_dual_plan).
  * 7: the BGK barrier pricer's Monte Carlo entry points (fdcn_mc_bgk_batch,
  * fdcn_mc_bgk_batch_dev, fdcn_mc_bgk_plan) were added after 6.
  * 6: the Monte Carlo discrete-barrier entry points (fdcn_mc_barrier_batch,
@@ -872,6 +874,110 @@ int fdcn_mc_lsm_div_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t ant
                               const double* div, uint64_t seed, int64_t obs_first, double* stats,
                               double* values_out, double* coef_out, double* workspace,
                               int64_t workspace_bytes, void* stream);
+
+/* ---- Dual upper bound for the least-squares Monte Carlo (Andersen-Broadie;
+ * csrc/fdcn_mc_dual.hip).  The out-of-sample LSM price is a lower bound; the
+ * policy it has fitted drives a nested simulation that gives a gap >= 0 with
+ * lower bound + gap an upper bound in expectation, whatever the policy.
+ * One launch takes B contracts that share n_steps, G, `antithetic`, n_outer
+ * and n_inner:
+ *   params, flags, step                 those of the fdcn_mc_lsm_batch launch
+ *   coef [B][G][n_steps][FDCN_LSM_NCOEF]  what that launch wrote to coef_out:
+ *                                       sub-run g's rows are sub-run g's policy
+ *   n_outer   outer paths per sub-run, 1 .. FDCN_DUAL_MAX_OUTER
+ *   n_inner   inner paths per start, a multiple of 256 (of 512 when
+ *             antithetic), up to FDCN_DUAL_MAX_INNER
+ *   subrun_first   the absolute number of this launch's sub-run 0 (a shard);
+ *             subrun_first + G <= 2^31
+ * Steps, events, eligibility and the fitted rule are phase C's above, word for
+ * word: on a knock-out a monitored breach is checked first and forces
+ * max(phi, REBATE_m); a knock-in path is eligible from its hit step on, that
+ * step included; the fitted rule stops on an EXERCISE step before maturity
+ * with a valid fit, eligible, phi > 0 and phi > fit(u); maturity always stops.
+ * Every cashflow is discounted to valuation: Z_m = phi * DF_END_m is the
+ * reward for stopping at m.  Every operation below is rounded separately.
+ *
+ * Per outer path: x = ln(spot), r = 0, D = -inf; for m = 1 .. n_steps,
+ * x += DRIFT_m + DIFF_m * z_m, then
+ *   forced stop (knock-out breach at a MONITOR step, or m = n_steps):
+ *       D = max(D, 0 - r); the path ends.
+ *   the holder may stop (m < n_steps, EXERCISE_m, eligible, phi > 0; the fit
+ *   need not be valid): the inner simulation gives C_m, the mean over n_inner
+ *   fresh paths started at (x, knocked-in state) of the discounted cashflow of
+ *   following phase C's rule from step m + 1 on; then
+ *       the fitted rule stops at m:  D = max(D, 0 - r), then r = r + (Z_m - C_m)
+ *       otherwise:                   D = max(D, (Z_m - C_m) - r)
+ *   any other step (no EXERCISE flag, not eligible, or phi == 0): nothing, and
+ *   no inner simulation.  A phi == 0 candidate cannot beat the next stop's,
+ *   because C_m >= 0: every cashflow is >= 0, for which REBATE_m >= 0 is
+ *   required (a negative one is refused by the host entry).
+ * D >= 0 exactly: at the policy's first stop, fitted or forced, r is still 0
+ * and the candidate is 0 - 0.  D == 0 for a contract without an EXERCISE step
+ * before maturity, and no inner path is run for it.
+ * C_m: inner path i of a start is slot k = i / 256 of thread i % 256; each
+ * thread adds its slots' cashflows in slot order, a fixed tree v[t] + v[t +
+ * off], off = 128 .. 1, adds the threads, and the total is divided by n_inner.
+ * The gap of a sub-run is the sum of its D in path order divided by n_outer;
+ * a second kernel adds the sub-run gaps in sub-run order.  No floating-point
+ * atomics.  A contract's numbers depend on neither B nor its position in the
+ * batch.
+ *
+ * Normals: the Philox mapping of fdcn_mc_lsm_batch with bit 31 of counter word
+ * 3 set, so the words are disjoint from the LSM's 2 * id and 2 * id + 1:
+ *   outer set  word 2^31 + 2 * id,      o = (subrun_first + g) * n_outer + p,
+ *              z_m = element (m - 1) % 2 of pair (m - 1) / 2
+ *   inner set  word 2^31 + 2 * id + 1,
+ *              o = ((((subrun_first + g) * 2^10 + p) * 2^9 + (m - 1)) * 2^14 + j
+ *              for observation j of the start at step m of outer path p: 31 +
+ *              10 + 9 + 14 = 64 bits at the caps, and injective; step m + 1 + t
+ *              of the inner path draws element t % 2 of pair t / 2.
+ * Without antithetic inner path i is observation i; with it a start has
+ * n_inner / 2 observations and path i is observation (k / 2) * 256 + i % 256
+ * with +z for k even and -z for k odd, as in the LSM.  The outer paths are not
+ * paired.  Disjoint sub-run ranges of one (seed, stream id) are shards of one
+ * run: their (G, sum, sum of squares) of the sub-run gaps merge.
+ *   stats [B][FDCN_DUAL_NSTAT]          see enum fdcn_dual_stat
+ *   gap_out  [B][G * n_outer]           D per outer path (NULL: none)
+ *   cont_out [B][G * n_outer][n_steps]  C_m, 0.0 where no inner simulation was
+ *                                       run (NULL: none)
+ * Cash dividends are out of scope: there is no `div` input.
+ * Validation (before any device call; FDCN_EINVAL): that of fdcn_mc_lsm_batch
+ * with subrun_first in the place of obs_first, and n_outer or n_inner out of
+ * range, NULL coef, and, host entry only, a negative REBATE on a barrier
+ * contract or a coefficient that is not finite. */
+#define FDCN_DUAL_MAX_OUTER 1024
+#define FDCN_DUAL_MAX_INNER 16384
+#define FDCN_DUAL_NSTAT 7
+enum fdcn_dual_stat {
+  FDCN_DUAL_O_GAP = 0,     /* mean of the sub-run gaps                            */
+  FDCN_DUAL_O_STDERR,      /* their sample standard deviation / sqrt(G); 0: G = 1 */
+  FDCN_DUAL_O_SUM,         /* sum of the sub-run gaps (merging)                   */
+  FDCN_DUAL_O_SUM2,        /* sum of their squares                                */
+  FDCN_DUAL_O_MIN_MARGIN,  /* min |phi - fit(u)| over every fitted decision taken,
+                              outer and inner; +inf if none                       */
+  FDCN_DUAL_O_INNER_PATHS, /* inner paths run: starts * n_inner                   */
+  FDCN_DUAL_O_INNER_STEPS  /* steps those paths walked until they stopped         */
+};
+/* Host pointers; copies in and out on the calling thread's stream and waits. */
+int fdcn_mc_lsm_dual_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                           int32_t n_outer, int32_t n_inner, const double* params,
+                           const int32_t* flags, const double* step, const double* coef,
+                           uint64_t seed, int64_t subrun_first, double* stats, double* gap_out,
+                           double* cont_out);
+/* Device pointers, asynchronous on `stream`, no host sync; `workspace` as in
+ * fdcn_mc_lsm_batch_dev, sized by fdcn_mc_lsm_dual_plan, or NULL.  The
+ * contents of the arrays are not checked here. */
+int fdcn_mc_lsm_dual_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                               int32_t n_outer, int32_t n_inner, const double* params,
+                               const int32_t* flags, const double* step, const double* coef,
+                               uint64_t seed, int64_t subrun_first, double* stats,
+                               double* gap_out, double* cont_out, double* workspace,
+                               int64_t workspace_bytes, void* stream);
+/* Geometry of a launch: workspace bytes per contract, doubles per contract of
+ * gap_out and of cont_out.  Any output pointer may be NULL.  Host only. */
+int fdcn_mc_lsm_dual_plan(int32_t n_steps, int32_t G, int32_t antithetic, int32_t n_outer,
+                          int32_t n_inner, int64_t* ws_bytes_per_contract,
+                          int64_t* gap_per_contract, int64_t* cont_per_contract);
 
 /* ---- host-side plan helpers (no device) -------------------------------- */
 /* Uniform log grid of the pricers' _build_log_grid

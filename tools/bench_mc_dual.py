@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""Throughput of the dual-bound kernel of the least-squares Monte Carlo
+(csrc/fdcn_mc_dual.hip).
+
+Device: `--contracts` contracts (bench_mc_lsm.py's batch: the seven barrier
+kinds in turn, spot and strike spread by a seeded draw) x `--subruns` sub-runs
+x `--outer` outer paths x `--inner` inner paths per start x `--steps` steps,
+antithetic, every array resident on the device.  One fdcn_mc_lsm_batch_dev
+launch fits the policies and leaves its coefficient dump on the device; then
+fdcn_mc_lsm_dual_batch_dev with a planned workspace: warm-up, `--launches`
+launches timed one by one with device events, the median is the result.  The
+unit is the inner path-step, one `x += drift + diff z` of one inner path, as
+the kernel itself counts them (FDCN_DUAL_O_INNER_STEPS: a path that has
+stopped walks no further, so the count is the work done, not paths x steps).
+
+Yardstick, same process: the NumPy host engine (mc_american.host_dual_subruns,
+the same estimator on the same streams under the same policies) on the first
+`--host-contracts` contracts x `--host-subruns` sub-runs, one thread.
+
+Prints one JSON line.  --dump-outputs DIR writes the stats of the last timed
+launch as DIR/mc_dual_stats.npy.  Without a GPU it fails; there is no fallback.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from bench_mc_lsm import build_batch  # noqa: E402
+
+
+def device_run(plans, G: int, n_outer: int, n_inner: int, launches: int, warmup: int, seed: int):
+    import torch
+    from finite_difference_amd import capi, mc_american
+    capi.require_device()
+    dev = torch.device("cuda:0")
+    B, n_steps = len(plans), plans[0].n_steps
+    P, F, S = mc_american._stack(plans, list(range(B)))
+    dP, dF, dS = (torch.from_numpy(a).to(dev) for a in (P, F, S))
+    lsm = capi.mc_lsm_plan(n_steps, G, True)
+    coef = torch.zeros((B, G, n_steps, capi.LSM_NCOEF), dtype=torch.float64, device=dev)
+    lsm_stats = torch.zeros((B, capi.LSM_NSTAT), dtype=torch.float64, device=dev)
+    stats = torch.zeros((B, capi.DUAL_NSTAT), dtype=torch.float64, device=dev)
+    plan = capi.mc_dual_plan(n_steps, G, True, n_outer, n_inner)
+    ws_bytes = max(plan["ws_bytes_per_contract"], lsm["ws_bytes_per_contract"]) * B
+    ws = torch.zeros(ws_bytes // 8, dtype=torch.float64, device=dev)
+    stream = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+
+    def launch():
+        capi.mc_dual_batch_dev(B, n_steps, G, True, n_outer, n_inner, dP.data_ptr(),
+                               dF.data_ptr(), dS.data_ptr(), coef.data_ptr(), seed, 0,
+                               stats.data_ptr(), None, None, ws.data_ptr(), ws_bytes,
+                               stream.cuda_stream)
+    times = []
+    with torch.cuda.stream(stream):
+        capi.mc_lsm_batch_dev(B, n_steps, G, True, dP.data_ptr(), dF.data_ptr(), dS.data_ptr(),
+                              seed, 0, lsm_stats.data_ptr(), None, coef.data_ptr(), ws.data_ptr(),
+                              ws_bytes, stream.cuda_stream)
+        for _ in range(warmup):
+            launch()
+        stream.synchronize()
+        for _ in range(launches):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(stream)
+            launch()
+            t1.record(stream)
+            t1.synchronize()
+            times.append(t0.elapsed_time(t1) * 1e-3)
+    return (times, stats.cpu().numpy(), lsm_stats.cpu().numpy(), coef.cpu().numpy(),
+            torch.cuda.get_device_name(0))
+
+
+def host_run(plans, coef, G: int, n_outer: int, n_inner: int, seed: int):
+    from finite_difference_amd import mc_american
+    steps = 0.0
+    t0 = time.perf_counter()
+    for b, c in enumerate(plans):
+        r = mc_american.host_dual_subruns(c, coef[b, :G], range(G), n_outer, n_inner, True, seed, b)
+        steps += float(r["inner_steps"].sum())
+    secs = time.perf_counter() - t0
+    return {"contracts": len(plans), "subruns": G, "threads": 1, "seconds": secs,
+            "inner_path_steps": steps, "inner_path_steps_per_s": steps / secs}
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--contracts", type=int, default=1024)
+    ap.add_argument("--subruns", type=int, default=32)
+    ap.add_argument("--outer", type=int, default=8)
+    ap.add_argument("--inner", type=int, default=2048)
+    ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--launches", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--host-contracts", type=int, default=7)
+    ap.add_argument("--host-subruns", type=int, default=1)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR")
+    args = ap.parse_args()
+
+    from finite_difference_amd import capi
+    plans = build_batch(args.contracts, args.steps)
+    times, stats, lsm_stats, coef, name = device_run(plans, args.subruns, args.outer, args.inner,
+                                                     args.launches, args.warmup, args.seed)
+    med = statistics.median(times)
+    steps = float(stats[:, capi.DUAL_O_INNER_STEPS].sum())
+    paths = float(stats[:, capi.DUAL_O_INNER_PATHS].sum())
+    rate = steps / med
+    nh = min(args.host_contracts, args.contracts)
+    host = host_run(plans[:nh], coef[:nh], min(args.host_subruns, args.subruns), args.outer,
+                    args.inner, args.seed)
+    gap, low = stats[:, capi.DUAL_O_GAP], lsm_stats[:, capi.LSM_O_PRICE]
+    line = {
+        "metric": "mc_dual_inner_path_steps_per_s",
+        "value": rate,
+        "device": name,
+        "contracts": args.contracts, "subruns": args.subruns, "n_outer": args.outer,
+        "n_inner": args.inner, "n_steps": args.steps, "antithetic": True,
+        "inner_paths_per_launch": paths, "inner_path_steps_per_launch": steps,
+        "launch_seconds": {"median": med, "min": min(times), "max": max(times),
+                           "launches": args.launches, "warmup": args.warmup},
+        "contracts_per_s": args.contracts / med,
+        "host_engine": host,
+        "speedup_over_host_engine": rate / host["inner_path_steps_per_s"],
+        "gap_range": [float(gap.min()), float(gap.max())],
+        "median_gap_over_lower_bound": float(np.median(gap / np.maximum(low, 1e-300))),
+    }
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "mc_dual_stats.npy"), stats)
+        line["dumped"] = {"mc_dual_stats": list(stats.shape)}
+    print(json.dumps(line))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
