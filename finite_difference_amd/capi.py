@@ -51,6 +51,9 @@ EXPORTED = ("fdcn_cn_batch", "fdcn_it_batch", "fdcn_cn_batch_dev", "fdcn_it_batc
             "fdcn_mc_lsm_batch", "fdcn_mc_lsm_batch_dev", "fdcn_mc_lsm_plan",
             "fdcn_mc_lsm_div_batch", "fdcn_mc_lsm_div_batch_dev",
             "fdcn_mc_lsm_dual_batch", "fdcn_mc_lsm_dual_batch_dev", "fdcn_mc_lsm_dual_plan",
+            "fdcn_mc_policy_batch", "fdcn_mc_policy_batch_dev", "fdcn_mc_policy_plan",
+            "fdcn_mc_policy_dual_batch", "fdcn_mc_policy_dual_batch_dev",
+            "fdcn_mc_policy_dual_plan",
             "fdcn_mc_qmc_batch", "fdcn_mc_qmc_batch_dev", "fdcn_mc_qmc_plan")
 # include/fdcn_diag.h: test / tuning entry points, not the product boundary
 DIAG_EXPORTED = ("fdcn_force_variant", "fdcn_forced_variant", "fdcn_variant_name",
@@ -86,6 +89,11 @@ LSM_F_PUT, LSM_F_KIND, LSM_F_STREAM = range(3)
 DUAL_MAX_OUTER, DUAL_MAX_INNER, DUAL_NSTAT = 1024, 16384, 7
 (DUAL_O_GAP, DUAL_O_STDERR, DUAL_O_SUM, DUAL_O_SUM2, DUAL_O_MIN_MARGIN, DUAL_O_INNER_PATHS,
  DUAL_O_INNER_STEPS) = range(7)
+# Monte Carlo under a given exercise table (enum fdcn_policy_col / _stat)
+POLICY_NCOL, POLICY_NSTAT = 2, 6
+POLICY_X_LO, POLICY_X_HI = range(2)
+(POLICY_O_PRICE, POLICY_O_STDERR, POLICY_O_SUM, POLICY_O_SUM2, POLICY_O_MIN_MARGIN,
+ POLICY_O_EXERCISED) = range(6)
 LSM_KIND = {"none": 0, "down-and-out": 1, "up-and-out": 2, "double-out": 3, "down-and-in": 4,
             "up-and-in": 5, "double-in": 6}
 
@@ -318,6 +326,21 @@ def lib() -> ctypes.CDLL:
                                                 ctypes.POINTER(ctypes.c_int64),
                                                 ctypes.POINTER(ctypes.c_int64),
                                                 ctypes.POINTER(ctypes.c_int64)]
+            L.fdcn_mc_policy_batch.restype = _I
+            L.fdcn_mc_policy_batch.argtypes = [_I, _I, _I, _I, _V, _V, _V, _V, ctypes.c_uint64,
+                                               _I64, _V, _V]
+            L.fdcn_mc_policy_batch_dev.restype = _I
+            L.fdcn_mc_policy_batch_dev.argtypes = [_I, _I, _I, _I, _V, _V, _V, _V,
+                                                   ctypes.c_uint64, _I64, _V, _V, _V, _I64, _V]
+            L.fdcn_mc_policy_plan.restype = _I
+            L.fdcn_mc_policy_plan.argtypes = [_I, _I, _I, _PI, ctypes.POINTER(ctypes.c_int64),
+                                              ctypes.POINTER(ctypes.c_int64)]
+            L.fdcn_mc_policy_dual_batch.restype = _I
+            L.fdcn_mc_policy_dual_batch.argtypes = L.fdcn_mc_lsm_dual_batch.argtypes
+            L.fdcn_mc_policy_dual_batch_dev.restype = _I
+            L.fdcn_mc_policy_dual_batch_dev.argtypes = L.fdcn_mc_lsm_dual_batch_dev.argtypes
+            L.fdcn_mc_policy_dual_plan.restype = _I
+            L.fdcn_mc_policy_dual_plan.argtypes = L.fdcn_mc_lsm_dual_plan.argtypes
             L.fdcn_mc_normals.restype = _I
             L.fdcn_mc_normals.argtypes = [_I64, _I, ctypes.c_uint64, _I, _I64, _V]
             L.fdcn_mc_qmc_batch.restype = _I
@@ -1041,3 +1064,106 @@ def mc_dual_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, n_outer: i
         int(B), int(n_steps), int(G), 1 if antithetic else 0, int(n_outer), int(n_inner),
         params_ptr, flags_ptr, step_ptr, coef_ptr, int(seed) & (2 ** 64 - 1), int(subrun_first),
         stats_ptr, gap_ptr, cont_ptr, workspace_ptr, int(workspace_bytes), stream_ptr))
+
+
+def mc_policy_plan(n_steps: int, G: int, antithetic: bool) -> dict:
+    """Geometry of a table-policy launch (fdcn_mc_policy_plan; host only):
+    observations per sub-run, workspace bytes per contract, doubles per
+    contract of the value dump."""
+    per = ctypes.c_int32()
+    ws, nv = ctypes.c_int64(), ctypes.c_int64()
+    _check(lib().fdcn_mc_policy_plan(int(n_steps), int(G), 1 if antithetic else 0,
+                                     ctypes.byref(per), ctypes.byref(ws), ctypes.byref(nv)))
+    return dict(obs_per_subrun=per.value, ws_bytes_per_contract=ws.value,
+                values_per_contract=nv.value)
+
+
+def _policy_arrays(who: str, params, flags, step, policy):
+    P = _f64(params).reshape(-1, LSM_NPARAM)
+    F = _i32(flags).reshape(-1, LSM_NFLAG)
+    S = _f64(step)
+    T = _f64(policy)
+    B = P.shape[0]
+    if F.shape[0] != B or S.ndim != 3 or S.shape[0] != B or S.shape[2] != LSM_NSTEP:
+        raise ValueError(f"{who}: params [B, 4], flags [B, 3], step [B, n_steps, 9]")
+    if T.shape != (B, S.shape[1], POLICY_NCOL):
+        raise ValueError(f"{who}: policy [B, n_steps, 2]")
+    return P, F, S, T
+
+
+def mc_policy_batch(params, flags, step, policy, G: int, antithetic: bool, *, seed: int = 0,
+                    obs_first: int = 0, want_values: bool = False):
+    """fdcn_mc_policy_batch on host arrays -> (stats [B, POLICY_NSTAT], values
+    [B, G * LSM_SUBRUN] or None).  params, flags, step as mc_lsm_batch; policy
+    [B, n_steps, POLICY_NCOL]."""
+    require_device()
+    P, F, S, T = _policy_arrays("mc_policy_batch", params, flags, step, policy)
+    B, n_steps, G = P.shape[0], S.shape[1], int(G)
+    stats = np.empty((B, POLICY_NSTAT), dtype=np.float64)
+    val = np.empty((B, max(G, 0) * LSM_SUBRUN), dtype=np.float64) if want_values else None
+    _check(lib().fdcn_mc_policy_batch(
+        B, n_steps, G, 1 if antithetic else 0, P.ctypes.data, F.ctypes.data, S.ctypes.data,
+        T.ctypes.data, int(seed) & (2 ** 64 - 1), int(obs_first), stats.ctypes.data,
+        val.ctypes.data if want_values else None))
+    return stats, val
+
+
+def mc_policy_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, params_ptr: int,
+                        flags_ptr: int, step_ptr: int, policy_ptr: int, seed: int,
+                        obs_first: int, stats_ptr: int, values_ptr: Optional[int],
+                        workspace_ptr: Optional[int], workspace_bytes: int,
+                        stream_ptr: Optional[int]) -> None:
+    """fdcn_mc_policy_batch_dev: every array already on the device;
+    asynchronous on `stream_ptr`."""
+    _check(lib().fdcn_mc_policy_batch_dev(
+        int(B), int(n_steps), int(G), 1 if antithetic else 0, params_ptr, flags_ptr, step_ptr,
+        policy_ptr, int(seed) & (2 ** 64 - 1), int(obs_first), stats_ptr, values_ptr,
+        workspace_ptr, int(workspace_bytes), stream_ptr))
+
+
+def mc_policy_dual_plan(n_steps: int, G: int, antithetic: bool, n_outer: int,
+                        n_inner: int) -> dict:
+    """Geometry of a table-policy dual launch (fdcn_mc_policy_dual_plan; host
+    only), as mc_dual_plan."""
+    ws, ng, nc = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    _check(lib().fdcn_mc_policy_dual_plan(int(n_steps), int(G), 1 if antithetic else 0,
+                                          int(n_outer), int(n_inner), ctypes.byref(ws),
+                                          ctypes.byref(ng), ctypes.byref(nc)))
+    return dict(ws_bytes_per_contract=ws.value, gap_per_contract=ng.value,
+                cont_per_contract=nc.value)
+
+
+def mc_policy_dual_batch(params, flags, step, policy, G: int, n_outer: int, n_inner: int,
+                         antithetic: bool, *, seed: int = 0, subrun_first: int = 0,
+                         want_gap: bool = False, want_cont: bool = False):
+    """fdcn_mc_policy_dual_batch on host arrays -> (stats [B, DUAL_NSTAT], gap
+    [B, G * n_outer] or None, cont [B, G * n_outer, n_steps] or None); policy
+    [B, n_steps, POLICY_NCOL]."""
+    require_device()
+    P, F, S, T = _policy_arrays("mc_policy_dual_batch", params, flags, step, policy)
+    B, n_steps, G, n_outer = P.shape[0], S.shape[1], int(G), int(n_outer)
+    stats = np.empty((B, DUAL_NSTAT), dtype=np.float64)
+    rows = max(G, 0) * max(n_outer, 0)
+    gap = np.empty((B, rows), dtype=np.float64) if want_gap else None
+    cont = np.empty((B, rows, n_steps), dtype=np.float64) if want_cont else None
+    _check(lib().fdcn_mc_policy_dual_batch(
+        B, n_steps, G, 1 if antithetic else 0, n_outer, int(n_inner), P.ctypes.data,
+        F.ctypes.data, S.ctypes.data, T.ctypes.data, int(seed) & (2 ** 64 - 1),
+        int(subrun_first), stats.ctypes.data, gap.ctypes.data if want_gap else None,
+        cont.ctypes.data if want_cont else None))
+    return stats, gap, cont
+
+
+def mc_policy_dual_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, n_outer: int,
+                             n_inner: int, params_ptr: int, flags_ptr: int, step_ptr: int,
+                             policy_ptr: int, seed: int, subrun_first: int, stats_ptr: int,
+                             gap_ptr: Optional[int], cont_ptr: Optional[int],
+                             workspace_ptr: Optional[int], workspace_bytes: int,
+                             stream_ptr: Optional[int]) -> None:
+    """fdcn_mc_policy_dual_batch_dev: every array already on the device;
+    asynchronous on `stream_ptr`."""
+    _check(lib().fdcn_mc_policy_dual_batch_dev(
+        int(B), int(n_steps), int(G), 1 if antithetic else 0, int(n_outer), int(n_inner),
+        params_ptr, flags_ptr, step_ptr, policy_ptr, int(seed) & (2 ** 64 - 1),
+        int(subrun_first), stats_ptr, gap_ptr, cont_ptr, workspace_ptr, int(workspace_bytes),
+        stream_ptr))

@@ -43,6 +43,15 @@ csrc/fdcn_mc_dual.hip on the device, ``host_dual_subruns`` in NumPy).
 ``brackets`` is the comparison of an FD price with the two bounds.  Cash
 dividends are out of scope there: a contract that carries them is refused.
 
+Both bounds also run under a *given* exercise rule instead of the fitted one
+(``mc_policy_batch``, ``mc_policy_bounds_batch``): an ``ExercisePolicy`` is a
+band in the log-spot per step, and ``policy_from_pricer`` builds it from the
+exercise boundary a BermudanFDMPricer has computed.  Any rule gives a lower
+bound and any rule gives a dual upper bound, so the FD boundary can drive
+both without circularity: a wrong boundary shows as a low lower bound and a
+wide gap, not as agreement (include/fdcn.h, fdcn_mc_policy_batch;
+csrc/fdcn_mc_policy.hip; ``host_policy_subruns`` in NumPy).
+
 A missing GPU under ``engine="hip"`` is an error, never a silent fallback.
 """
 from __future__ import annotations
@@ -60,7 +69,11 @@ from .mc_barrier import philox4x32_10, philox_normals
 __all__ = ["LsmContract", "LsmConfig", "plan_american_contract", "contract_from_pricer",
            "simulate_lsm", "price_american_mc", "mc_american_batch", "merge_lsm_stats",
            "DualConfig", "host_dual_subruns", "simulate_dual", "mc_american_bounds_batch",
-           "price_american_mc_bounds", "merge_dual_stats", "brackets"]
+           "price_american_mc_bounds", "merge_dual_stats", "brackets",
+           "ExercisePolicy", "policy_from_pricer", "host_policy_subruns",
+           "host_policy_dual_subruns", "simulate_policy", "simulate_policy_dual",
+           "mc_policy_batch", "price_policy_mc", "mc_policy_bounds_batch",
+           "price_policy_mc_bounds", "merge_policy_stats"]
 
 _KO = ("down-and-out", "up-and-out", "double-out")
 _KI = ("down-and-in", "up-and-in", "double-in")
@@ -799,6 +812,46 @@ def _check_dual_contract(c: LsmContract) -> None:
         raise ValueError("a negative rebate: the dual bound needs every cashflow >= 0.")
 
 
+class _FittedRule:
+    """Phase C's fitted rule for the dual walks: coef [g, n_steps, LSM_NCOEF],
+    row crow[r] for outer path r."""
+
+    def __init__(self, c: LsmContract, coef: np.ndarray, crow: np.ndarray):
+        self.coef, self.crow = coef, crow
+        self.centre, self.iscale = c.step[:, capi.LSM_S_CENTRE], c.step[:, capi.LSM_S_ISCALE]
+
+    def any_at(self, rows, i) -> bool:
+        return bool(np.any(self.coef[self.crow[rows], i, 4] != 0.0))
+
+    def decide(self, rows, i, x, phi, live):
+        """(stops, distance to the decision's edge; inf where none is taken)
+        for the paths x of the outer paths `rows` (axis 0) at 0-based step i."""
+        cc = self.coef[self.crow[rows], i]
+        if x.ndim == 2:
+            cc = cc[:, None, :]
+        u = (x - self.centre[i]) * self.iscale[i]
+        fit = cc[..., 0] + u * (cc[..., 1] + u * (cc[..., 2] + u * cc[..., 3]))
+        cand = live & (cc[..., 4] != 0.0) & (phi > 0.0)
+        return cand & (phi > fit), np.where(cand, np.abs(phi - fit), np.inf)
+
+
+class _TableRule:
+    """The table rule (include/fdcn.h, fdcn_mc_policy_batch): stop in the band
+    [X_LO, X_HI] of the step where phi > 0; the decision is taken, and its
+    margin counted, whatever phi is."""
+
+    def __init__(self, policy: "ExercisePolicy"):
+        self.lo, self.hi = policy.x_lo, policy.x_hi
+
+    def any_at(self, rows, i) -> bool:
+        return True
+
+    def decide(self, rows, i, x, phi, live):
+        lo, hi = self.lo[i], self.hi[i]
+        gap = np.minimum(np.abs(x - lo), np.abs(x - hi))
+        return live & (lo <= x) & (x <= hi) & (phi > 0.0), np.where(live, gap, np.inf)
+
+
 def host_dual_subruns(c: LsmContract, coef: np.ndarray, subruns: Sequence[int], n_outer: int,
                       n_inner: int, antithetic: bool, seed: int, stream_id: int) -> dict:
     """The dual estimator for the sub-runs `subruns` (absolute numbers) of
@@ -807,13 +860,20 @@ def host_dual_subruns(c: LsmContract, coef: np.ndarray, subruns: Sequence[int], 
     n_outer outer paths side by side.  -> gaps [g, n_outer] (D per outer
     path), cont [g, n_outer, n_steps] (the inner means, 0.0 where none was
     run), margin [g], inner_paths [g], inner_steps [g]."""
+    coef = np.asarray(coef, dtype=float)
+    if coef.shape != (len(subruns), c.n_steps, capi.LSM_NCOEF):
+        raise ValueError("host_dual_subruns: coef [len(subruns), n_steps, LSM_NCOEF]")
+    rule = _FittedRule(c, coef, np.repeat(np.arange(len(subruns)), int(n_outer)))
+    return _host_dual(c, rule, subruns, n_outer, n_inner, antithetic, seed, stream_id)
+
+
+def _host_dual(c: LsmContract, rule, subruns: Sequence[int], n_outer: int, n_inner: int,
+               antithetic: bool, seed: int, stream_id: int) -> dict:
+    """host_dual_subruns under `rule` (_FittedRule or _TableRule)."""
     _check_dual_sizes(n_outer, n_inner, bool(antithetic))
     _check_dual_contract(c)
     P, F, S = c.params, c.flags, c.step
     M, ng = c.n_steps, len(subruns)
-    coef = np.asarray(coef, dtype=float)
-    if coef.shape != (ng, M, capi.LSM_NCOEF):
-        raise ValueError("host_dual_subruns: coef [len(subruns), n_steps, LSM_NCOEF]")
     if any(not 0 <= int(g) < 2 ** 31 for g in subruns):
         raise ValueError("host_dual_subruns: sub-run numbers must be in 0 .. 2^31 - 1")
     strike, lower, upper = float(P[capi.LSM_P_STRIKE]), float(P[capi.LSM_P_LOWER]), \
@@ -849,12 +909,10 @@ def host_dual_subruns(c: LsmContract, coef: np.ndarray, subruns: Sequence[int], 
     exr = S[:, capi.LSM_S_EXERCISE] != 0.0
     exr[M - 1] = False
     reb, dfe = S[:, capi.LSM_S_REBATE], S[:, capi.LSM_S_DF_END]
-    centre, iscale = S[:, capi.LSM_S_CENTRE], S[:, capi.LSM_S_ISCALE]
 
     R = ng * n_outer                                   # outer paths, row = g * n_outer + p
     sub = np.repeat(np.asarray([int(g) for g in subruns], dtype=np.uint64), n_outer)
     pth = np.tile(np.arange(n_outer, dtype=np.uint64), ng)
-    crow = np.repeat(np.arange(ng), n_outer)           # coefficient row of an outer path
     Zo = _normals_at(sub * np.uint64(n_outer) + pth, M, seed, w_outer)
     margin = np.full(R, np.inf)
     walked = np.zeros(R)
@@ -870,7 +928,6 @@ def host_dual_subruns(c: LsmContract, coef: np.ndarray, subruns: Sequence[int], 
         z = _normals_at(base[:, None] + np.arange(n_obs, dtype=np.uint64)[None, :], n_rem, seed,
                         w_inner)
         n = len(rows)
-        cr = coef[crow[rows]]                          # [n, M, NCOEF]
         x = np.repeat(x_start[:, None], n_inner, axis=1)
         inn = np.repeat(in_start[:, None], n_inner, axis=1)
         val = np.zeros((n, n_inner))
@@ -881,8 +938,8 @@ def host_dual_subruns(c: LsmContract, coef: np.ndarray, subruns: Sequence[int], 
             ii = i + 1 + t
             walked[rows] += np.sum(~done, axis=1)
             x = x + (drift[ii] + diff[ii] * (z[:, obs_of, t] * sign[None, :]))
-            fitted = (cr[:, ii, 4] != 0.0)[:, None] & bool(exr[ii])
-            if not (mon[ii] or ii == M - 1 or fitted.any()):
+            ruled = bool(exr[ii]) and rule.any_at(rows, ii)
+            if not (mon[ii] or ii == M - 1 or ruled):
                 continue
             s = np.exp(x)
             phi = payoff(s)
@@ -897,16 +954,11 @@ def host_dual_subruns(c: LsmContract, coef: np.ndarray, subruns: Sequence[int], 
             if ii == M - 1:
                 val = np.where(~done, np.where(elig, phi, reb[ii]) * dfe[ii], val)
                 done[:] = True
-            else:
-                cand = ~done & fitted & elig & (phi > 0.0)
-                if cand.any():
-                    u = (x - centre[ii]) * iscale[ii]
-                    fit = _cubic(cr[:, ii, :4], u)
-                    gap = np.where(cand, np.abs(phi - fit), np.inf)
-                    margin[rows] = np.minimum(margin[rows], gap.min(axis=1))
-                    go = cand & (phi > fit)
-                    val = np.where(go, phi * dfe[ii], val)
-                    done |= go
+            elif ruled:
+                go, gap = rule.decide(rows, ii, x, phi, ~done & elig)
+                margin[rows] = np.minimum(margin[rows], gap.min(axis=1))
+                val = np.where(go, phi * dfe[ii], val)
+                done |= go
         return _block_sum(val) / float(n_inner)
 
     x = np.full(R, x0)
@@ -926,21 +978,17 @@ def host_dual_subruns(c: LsmContract, coef: np.ndarray, subruns: Sequence[int], 
         if ki:
             inn = inn | (hit & alive)
         elig = inn if ki else np.ones(R, dtype=bool)
-        start = alive & ~forced & bool(exr[i]) & elig & (phi > 0.0)
-        rows_all = np.nonzero(start)[0]
+        live = alive & ~forced & bool(exr[i]) & elig
+        go, gap = rule.decide(np.arange(R), i, x, phi, live)
+        margin = np.minimum(margin, gap)
+        rows_all = np.nonzero(live & (phi > 0.0))[0]
         per = max(1, _INNER_CHUNK // max(1, n_inner * (M - 1 - i)))
         for lo in range(0, len(rows_all), per):
             rows = rows_all[lo:lo + per]
             chat = inner(rows, i, x[rows], inn[rows])
             cont[rows, i] = chat
             starts[rows] += 1.0
-            cc = coef[crow[rows], i]
-            valid = cc[:, 4] != 0.0
-            u = (x[rows] - centre[i]) * iscale[i]
-            fit = cc[:, 0] + u * (cc[:, 1] + u * (cc[:, 2] + u * cc[:, 3]))
-            margin[rows] = np.where(valid, np.minimum(margin[rows], np.abs(phi[rows] - fit)),
-                                    margin[rows])
-            stops = valid & (phi[rows] > fit)
+            stops = go[rows]
             zc = phi[rows] * dfe[i] - chat
             D[rows] = np.where(stops, np.maximum(D[rows], 0.0 - r[rows]),
                                np.maximum(D[rows], zc - r[rows]))
@@ -1164,3 +1212,499 @@ def brackets(result: dict, fd_price: float, grid_error: float = 0.0, z: float = 
     lower = float(result["price"]) - z * float(result["stderr"]) - float(grid_error)
     upper = float(result["upper"]) + z * float(result["upper_stderr"]) + float(grid_error)
     return bool(lower <= float(fd_price) <= upper)
+
+
+# ---------------------------------------------------------------------------
+# bounds under a given exercise table (include/fdcn.h, fdcn_mc_policy_batch)
+# ---------------------------------------------------------------------------
+@dataclass
+class ExercisePolicy:
+    """A per-step exercise rule: at step m the holder stops where the path is
+    eligible, X_LO_m <= ln(s) <= X_HI_m (both ends inclusive) and the payoff
+    is positive.  +-inf are legal, x_lo > x_hi means never at that step, and
+    a row on a step without an EXERCISE flag is ignored."""
+    x_lo: np.ndarray   # [n_steps]
+    x_hi: np.ndarray   # [n_steps]
+
+    def __post_init__(self):
+        self.x_lo = np.array(self.x_lo, dtype=float)
+        self.x_hi = np.array(self.x_hi, dtype=float)
+        if self.x_lo.ndim != 1 or self.x_lo.shape != self.x_hi.shape or self.x_lo.size < 1:
+            raise ValueError("ExercisePolicy: x_lo and x_hi are shaped [n_steps]")
+        if np.isnan(self.x_lo).any() or np.isnan(self.x_hi).any():
+            raise ValueError("ExercisePolicy: a NaN entry (+-inf are legal)")
+
+    @property
+    def n_steps(self) -> int:
+        return self.x_lo.shape[0]
+
+    def table(self) -> np.ndarray:
+        """[n_steps, POLICY_NCOL], the engines' layout."""
+        return np.stack([self.x_lo, self.x_hi], axis=1)
+
+    @classmethod
+    def never(cls, n_steps: int) -> "ExercisePolicy":
+        return cls(np.full(n_steps, np.inf), np.full(n_steps, -np.inf))
+
+    @classmethod
+    def always(cls, n_steps: int) -> "ExercisePolicy":
+        return cls(np.full(n_steps, -np.inf), np.full(n_steps, np.inf))
+
+    @classmethod
+    def from_critical_spots(cls, contract: LsmContract, spots: Dict) -> "ExercisePolicy":
+        """The threshold policy of `contract` from {t_m: (s_below, s_above)}:
+        the two spots between which exercise stops being optimal at the
+        exercise time t_m (matched to the contract's steps within 1e-12), or
+        None for "never at t_m".  A put stops at and below the midpoint in
+        log-spot of the pair (X_LO = -inf), a call at and above it (X_HI =
+        +inf); s_below = 0 or s_above = inf puts the threshold at that end.
+        Every EXERCISE step before maturity needs an entry, and every entry a
+        step; the other steps get "never"."""
+        M = contract.n_steps
+        put = bool(contract.flags[capi.LSM_F_PUT])
+        pol = cls.never(M)
+        ex = contract.step[:, capi.LSM_S_EXERCISE] != 0.0
+        ex[M - 1] = False
+        seen = np.zeros(M, dtype=bool)
+        for t, pair in spots.items():
+            i = int(np.argmin(np.abs(contract.times - float(t))))
+            if abs(float(contract.times[i]) - float(t)) > _MERGE or seen[i]:
+                raise ValueError(f"from_critical_spots: time {t!r} is not one step of the contract")
+            seen[i] = True
+            if pair is None:
+                continue
+            below, above = float(pair[0]), float(pair[1])
+            if not 0.0 <= below <= above or math.isnan(above):
+                raise ValueError("from_critical_spots: 0 <= s_below <= s_above")
+            with np.errstate(divide="ignore"):
+                mid = 0.5 * (float(np.log(below)) + float(np.log(above)))
+            if math.isnan(mid):  # (0, inf): everywhere
+                mid = math.inf if put else -math.inf
+            if put:
+                pol.x_lo[i], pol.x_hi[i] = -math.inf, mid
+            else:
+                pol.x_lo[i], pol.x_hi[i] = mid, math.inf
+        if np.any(ex & ~seen):
+            m = int(np.nonzero(ex & ~seen)[0][0]) + 1
+            raise ValueError(f"from_critical_spots: exercise step {m} (t = "
+                             f"{float(contract.times[m - 1])!r}) has no entry")
+        return pol
+
+
+def policy_from_pricer(p, contract: Optional[LsmContract] = None,
+                       n_time: Optional[int] = None) -> ExercisePolicy:
+    """The exercise boundary of the BermudanFDMPricer `p` as the policy of
+    `contract` (default: contract_from_pricer(p)).
+
+    `p.exercise_boundary(n_time)` gives, per exercise date, the nodes at which
+    the payoff exceeded the continuation value; its records are matched to
+    the contract's steps by time (within 1e-12), and an exercise step without
+    a record is an error.  A put stops at and below X_HI, the midpoint in
+    log-spot of s_nodes[hi] and s_nodes[hi + 1] (X_LO = -inf); a call at and
+    above X_LO, the midpoint of s_nodes[lo - 1] and s_nodes[lo] (X_HI = +inf);
+    a record with count == 0 gives "never".  The exact sign change lies
+    between those two nodes: the midpoint halves the worst case, and any
+    threshold is a valid policy -- it can only lower the lower bound and
+    widen the gap.
+
+    Only a BermudanFDMPricer is taken: its exercise dates are calendar dates
+    that coincide with the contract's steps, while the American classes are
+    simulated on the grid k T / n_exercise, which no boundary record lies on.
+    A knock-in contract takes the policy of a vanilla Bermudan twin: give the
+    twin as `p` and the knock-in contract (same exercise times) as `contract`;
+    the Monte Carlo applies the rule from the hit step on.  Pricers with cash
+    dividends are refused: they are out of the table policy's scope."""
+    from .bermudan import BermudanFDMPricer
+    if not isinstance(p, BermudanFDMPricer):
+        raise ValueError(f"policy_from_pricer takes a BermudanFDMPricer, not {type(p).__name__}: "
+                         "only Bermudan exercise dates coincide with the contract's steps (the "
+                         "American classes are simulated on the grid k T / n_exercise).")
+    if p._div_times_tau():
+        raise ValueError("cash dividends are out of the table policy's scope.")
+    if contract is None:
+        contract = contract_from_pricer(p)
+    if contract.has_dividends:
+        raise ValueError("cash dividends are out of the table policy's scope.")
+    put = p.option_type == "put"
+    if put != bool(contract.flags[capi.LSM_F_PUT]):
+        raise ValueError("policy_from_pricer: the pricer and the contract differ in option type")
+    recs = p.exercise_boundary(n_time)
+    s = np.asarray(p.s_nodes, dtype=float)
+    n = s.shape[0]
+    spots: Dict[float, Optional[tuple]] = {}
+    for _date, t, _s_star, lo, hi, count in recs:
+        if count == 0:
+            spots[t] = None
+        elif put:
+            spots[t] = (float(s[hi]), float(s[hi + 1]) if hi + 1 < n else math.inf)
+        else:
+            spots[t] = (float(s[lo - 1]) if lo >= 1 else 0.0, float(s[lo]))
+    return ExercisePolicy.from_critical_spots(contract, spots)
+
+
+def _check_policy(c: LsmContract, policy: ExercisePolicy) -> None:
+    if not isinstance(policy, ExercisePolicy):
+        raise TypeError("an ExercisePolicy per contract")
+    if policy.n_steps != c.n_steps:
+        raise ValueError(f"the policy has {policy.n_steps} steps, the contract {c.n_steps}")
+    if c.has_dividends:
+        raise ValueError("cash dividends are out of the table policy's scope.")
+
+
+def host_policy_subruns(c: LsmContract, policy: ExercisePolicy, subruns: Sequence[int],
+                        antithetic: bool, seed: int, stream_id: int) -> dict:
+    """The sub-runs `subruns` of contract c under `policy` on the host: the
+    kernel's operations per path on the LSM's price-set streams.  -> values
+    [g, LSM_SUBRUN], stop_step [g, LSM_SUBRUN] (the step m at which each path
+    stopped), means [g] (the kernel's sum: slot order, then the fixed tree),
+    margin [g], exercised [g] (paths the rule stopped)."""
+    _check_policy(c, policy)
+    P, F, S = c.params, c.flags, c.step
+    M, ng, n = c.n_steps, len(subruns), capi.LSM_SUBRUN
+    strike, lower, upper = float(P[capi.LSM_P_STRIKE]), float(P[capi.LSM_P_LOWER]), \
+        float(P[capi.LSM_P_UPPER])
+    put, kind = bool(F[capi.LSM_F_PUT]), int(F[capi.LSM_F_KIND])
+    ko, ki = 1 <= kind <= 3, kind >= 4
+    has_lo, has_hi = kind in (1, 3, 4, 6), kind in (2, 3, 5, 6)
+    x0 = float(np.log(P[capi.LSM_P_SPOT]))
+    per = obs_per_subrun(antithetic)
+
+    def payoff(s):
+        return np.maximum(strike - s, 0.0) if put else np.maximum(s - strike, 0.0)
+
+    def breach(s):
+        out = np.zeros(s.shape, dtype=bool)
+        if has_lo:
+            out |= s <= lower
+        if has_hi:
+            out |= s >= upper
+        return out
+
+    drift, diff = S[:, capi.LSM_S_DRIFT], S[:, capi.LSM_S_DIFF]
+    mon = (S[:, capi.LSM_S_MONITOR] != 0.0) & (kind != 0)
+    exr = S[:, capi.LSM_S_EXERCISE] != 0.0
+    exr[M - 1] = False
+    reb, dfe = S[:, capi.LSM_S_REBATE], S[:, capi.LSM_S_DF_END]
+    rule = _TableRule(policy)
+    Z = np.stack([_path_normals(M, seed, 2 * int(stream_id) + 1, int(g) * per, antithetic)
+                  for g in subruns])
+    x = np.full((ng, n), x0)
+    val = np.zeros((ng, n))
+    stop = np.zeros((ng, n), dtype=np.int64)
+    done = np.zeros((ng, n), dtype=bool)
+    inn = np.zeros((ng, n), dtype=bool)
+    margin = np.full(ng, np.inf)
+    exercised = np.zeros(ng)
+    for m in range(1, M + 1):
+        i = m - 1
+        x = x + (drift[i] + diff[i] * Z[:, :, i])
+        if not (mon[i] or exr[i] or m == M):
+            continue
+        s = np.exp(x)
+        phi = payoff(s)
+        hit = breach(s) if mon[i] else np.zeros((ng, n), dtype=bool)
+        if ko:
+            k = hit & ~done
+            val = np.where(k, np.maximum(phi, reb[i]) * dfe[i], val)
+            stop[k] = m
+            done |= k
+        if ki:
+            inn |= hit & ~done
+        elig = inn if ki else np.ones((ng, n), dtype=bool)
+        if m == M:
+            val = np.where(~done, np.where(elig, phi, reb[i]) * dfe[i], val)
+            stop[~done] = m
+            done[:] = True
+        elif exr[i]:
+            go, gap = rule.decide(None, i, x, phi, ~done & elig)
+            margin = np.minimum(margin, gap.min(axis=1))
+            val = np.where(go, phi * dfe[i], val)
+            stop[go] = m
+            done |= go
+            exercised += go.sum(axis=1)
+    return dict(values=val, stop_step=stop, means=_block_sum(val) / float(n), margin=margin,
+                exercised=exercised)
+
+
+def host_policy_dual_subruns(c: LsmContract, policy: ExercisePolicy, subruns: Sequence[int],
+                             n_outer: int, n_inner: int, antithetic: bool, seed: int,
+                             stream_id: int) -> dict:
+    """host_dual_subruns under the table `policy` (one for all sub-runs) in the
+    place of the fitted coefficients: the same streams, sums and outputs."""
+    _check_policy(c, policy)
+    return _host_dual(c, _TableRule(policy), subruns, n_outer, n_inner, antithetic, seed,
+                      stream_id)
+
+
+def _finalize_policy(means: np.ndarray, margin: float, exercised: float) -> np.ndarray:
+    """One row of stats [POLICY_NSTAT] from the sub-run means, the finalize
+    kernel's sums in its order."""
+    G = means.shape[0]
+    s, s2 = 0.0, 0.0
+    for g in range(G):
+        s += float(means[g])
+        s2 += float(means[g]) * float(means[g])
+    n = float(G)
+    se = math.sqrt(max(0.0, s2 - s * s / n) / (n - 1.0) / n) if G > 1 else 0.0
+    return np.array([s / n, se, s, s2, float(margin), float(exercised)])
+
+
+def merge_policy_stats(parts) -> Dict[str, float]:
+    """merge_lsm_stats for the result dicts of mc_policy_batch (or (G, sum, sum
+    of squares) tuples) of disjoint sub-run ranges of one contract; the dual
+    part merges through merge_dual_stats.  "exercised" adds up."""
+    parts = list(parts)
+    out = merge_lsm_stats(parts)
+    if all(isinstance(part, dict) for part in parts):
+        out["exercised"] = int(sum(part["exercised"] for part in parts))
+        out["min_margin"] = min(float(part["min_margin"]) for part in parts)
+    return out
+
+
+def _policy_group(who: str, group, policies, n_subruns, subrun_first, stream_ids, engine):
+    if engine not in ("hip", "host"):
+        raise ValueError("engine must be 'hip' or 'host'")
+    B = len(group)
+    if B < 1:
+        raise ValueError(f"{who}: no contracts")
+    if len(policies) != B:
+        raise ValueError(f"{who}: one policy per contract")
+    n_steps = group[0].n_steps
+    if any(c.n_steps != n_steps for c in group):
+        raise ValueError(f"{who}: the contracts of a launch share n_steps")
+    if n_steps > capi.LSM_MAX_STEPS:
+        raise ValueError(f"{who}: at most {capi.LSM_MAX_STEPS} steps")
+    for c, pol in zip(group, policies):
+        _check_policy(c, pol)
+    G = int(n_subruns)
+    if G < 1:
+        raise ValueError(f"{who}: n_subruns must be >= 1")
+    first = int(subrun_first)
+    if first != subrun_first or first < 0 or first + G > 2 ** 31:
+        raise ValueError(f"{who}: subrun_first must be a whole, non-negative number of sub-runs "
+                         "with subrun_first + n_subruns <= 2^31")
+    ids = list(range(B)) if stream_ids is None else [int(s) for s in stream_ids]
+    if len(ids) != B:
+        raise ValueError(f"{who}: one stream id per contract")
+    if any(not 0 <= s < 2 ** 30 for s in ids):
+        raise ValueError(f"{who}: stream ids must be in 0 .. 2^30 - 1")
+    return B, n_steps, G, first, ids
+
+
+def simulate_policy(group: Sequence[LsmContract], policies: Sequence[ExercisePolicy],
+                    n_subruns: int, antithetic: bool, *, engine: str = "hip", seed: int = 0,
+                    stream_ids: Optional[Sequence[int]] = None, subrun_first: int = 0,
+                    want_values: bool = False, host_chunk: int = 16) -> dict:
+    """simulate_lsm under given policies, one per contract: -> {"stats":
+    [B, POLICY_NSTAT]} plus "values" [B, n_subruns * LSM_SUBRUN] where asked
+    for, the paths those of simulate_lsm's "values"."""
+    B, n_steps, G, first, ids = _policy_group("simulate_policy", group, policies, n_subruns,
+                                              subrun_first, stream_ids, engine)
+    antithetic = bool(antithetic)
+    if engine == "hip":
+        capi.require_device()
+        P, F, S = _stack(group, ids)
+        T = np.stack([pol.table() for pol in policies])
+        stats, val = capi.mc_policy_batch(P, F, S, T, G, antithetic, seed=seed,
+                                          obs_first=first * obs_per_subrun(antithetic),
+                                          want_values=want_values)
+    else:
+        stats = np.empty((B, capi.POLICY_NSTAT))
+        val = np.empty((B, G * capi.LSM_SUBRUN)) if want_values else None
+        step = max(1, int(host_chunk))
+        for b, (c, pol) in enumerate(zip(group, policies)):
+            means = np.empty(G)
+            margin, exercised = math.inf, 0.0
+            for lo in range(0, G, step):
+                hi = min(G, lo + step)
+                r = host_policy_subruns(c, pol, range(first + lo, first + hi), antithetic, seed,
+                                        ids[b])
+                means[lo:hi] = r["means"]
+                margin = min(margin, float(r["margin"].min()))
+                exercised += float(r["exercised"].sum())
+                if want_values:
+                    val[b, lo * capi.LSM_SUBRUN:hi * capi.LSM_SUBRUN] = r["values"].reshape(-1)
+            stats[b] = _finalize_policy(means, margin, exercised)
+    out = {"stats": stats}
+    if want_values:
+        out["values"] = val
+    return out
+
+
+def simulate_policy_dual(group: Sequence[LsmContract], policies: Sequence[ExercisePolicy],
+                         n_subruns: int, n_outer: int, n_inner: int, antithetic: bool, *,
+                         engine: str = "hip", seed: int = 0,
+                         stream_ids: Optional[Sequence[int]] = None, subrun_first: int = 0,
+                         want_gap: bool = False, want_cont: bool = False,
+                         host_chunk: int = 16) -> dict:
+    """simulate_dual under given policies, one per contract: -> {"stats":
+    [B, DUAL_NSTAT]} plus "gap" [B, G * n_outer] and "cont" [B, G * n_outer,
+    n_steps] where asked for."""
+    B, n_steps, G, first, ids = _policy_group("simulate_policy_dual", group, policies,
+                                              n_subruns, subrun_first, stream_ids, engine)
+    antithetic = bool(antithetic)
+    _check_dual_sizes(n_outer, n_inner, antithetic)
+    n_outer, n_inner = int(n_outer), int(n_inner)
+    for c in group:
+        _check_dual_contract(c)
+    if engine == "hip":
+        capi.require_device()
+        P, F, S = _stack(group, ids)
+        T = np.stack([pol.table() for pol in policies])
+        stats, gap, cont = capi.mc_policy_dual_batch(
+            P, F, S, T, G, n_outer, n_inner, antithetic, seed=seed, subrun_first=first,
+            want_gap=want_gap, want_cont=want_cont)
+    else:
+        stats = np.empty((B, capi.DUAL_NSTAT))
+        gap = np.empty((B, G * n_outer))
+        cont = np.empty((B, G * n_outer, n_steps)) if want_cont else None
+        step = max(1, int(host_chunk))
+        for b, (c, pol) in enumerate(zip(group, policies)):
+            margin, paths, steps = math.inf, 0.0, 0.0
+            for lo in range(0, G, step):
+                hi = min(G, lo + step)
+                r = host_policy_dual_subruns(c, pol, range(first + lo, first + hi), n_outer,
+                                             n_inner, antithetic, seed, ids[b])
+                gap[b, lo * n_outer:hi * n_outer] = r["gaps"].reshape(-1)
+                if want_cont:
+                    cont[b, lo * n_outer:hi * n_outer] = r["cont"].reshape(-1, n_steps)
+                margin = min(margin, float(r["margin"].min()))
+                paths += float(r["inner_paths"].sum())
+                steps += float(r["inner_steps"].sum())
+            stats[b] = _finalize_dual(gap[b].reshape(G, n_outer), margin, paths, steps)
+        if not want_gap:
+            gap = None
+    out = {"stats": stats}
+    if want_gap:
+        out["gap"] = gap
+    if want_cont:
+        out["cont"] = cont
+    return out
+
+
+def _policy_result(c: LsmContract, G: int, st: Optional[np.ndarray]) -> dict:
+    if st is None:  # answered by the pricer's own rule, nothing simulated
+        price = float(c.fixed_price)
+        st = np.array([price, 0.0, price * G, price * price * G, math.inf, 0.0])
+        n_paths = 0
+    else:
+        n_paths = G * capi.LSM_SUBRUN
+    price, stderr = float(st[capi.POLICY_O_PRICE]), float(st[capi.POLICY_O_STDERR])
+    return {
+        "price": price,
+        "stderr": stderr,
+        "ci_95": (price - 1.96 * stderr, price + 1.96 * stderr),
+        "n_paths": int(n_paths),
+        "n_subruns": int(G),
+        "steps": int(c.n_steps),
+        "min_margin": float(st[capi.POLICY_O_MIN_MARGIN]),
+        "exercised": int(st[capi.POLICY_O_EXERCISED]),
+        "barrier_type": c.barrier_type,
+        "sum_mean": float(st[capi.POLICY_O_SUM]),
+        "sum_mean2": float(st[capi.POLICY_O_SUM2]),
+    }
+
+
+def _policy_batches(contracts, policies, cfg: LsmConfig, subrun_range, stream_ids):
+    plans = list(contracts)
+    if any(not isinstance(c, LsmContract) for c in plans):
+        raise TypeError("the table policy takes LsmContract objects (a policy is made for one)")
+    policies = list(policies)
+    if len(policies) != len(plans):
+        raise ValueError("one policy per contract")
+    for c, pol in zip(plans, policies):
+        if c.fixed_price is None:
+            _check_policy(c, pol)
+    lo, hi = 0, int(cfg.n_subruns)
+    if hi < 1:
+        raise ValueError("cfg.n_subruns must be positive.")
+    if subrun_range is not None:
+        lo, hi = subrun_range.start, subrun_range.stop
+        if subrun_range.step != 1 or not 0 <= lo < hi <= cfg.n_subruns:
+            raise ValueError("subrun_range must be a non-empty contiguous range within the "
+                             "contract's sub-runs")
+    ids = list(range(len(plans))) if stream_ids is None else [int(s) for s in stream_ids]
+    if len(ids) != len(plans):
+        raise ValueError("one stream id per contract")
+    by_steps: Dict[int, List[int]] = {}
+    for k, c in enumerate(plans):
+        if c.fixed_price is None:
+            by_steps.setdefault(c.n_steps, []).append(k)
+    return plans, policies, lo, hi, ids, by_steps
+
+
+def mc_policy_batch(contracts: Sequence[LsmContract], policies: Sequence[ExercisePolicy],
+                    cfg: LsmConfig = LsmConfig(), *, engine: str = "hip",
+                    stream_ids: Optional[Sequence[int]] = None,
+                    subrun_range: Optional[range] = None) -> List[dict]:
+    """The lower bound of many contracts under given policies, one launch per
+    distinct step count; arguments as mc_american_batch.  A `fixed_price`
+    contract is answered without a launch (its policy is not read).  Results,
+    in input order: price, stderr, ci_95, n_paths, n_subruns, steps,
+    min_margin (the smallest distance of a decision's log-spot to a finite
+    threshold), exercised (paths the rule stopped), barrier_type, sum_mean and
+    sum_mean2 (merge_policy_stats)."""
+    plans, policies, lo, hi, ids, by_steps = _policy_batches(contracts, policies, cfg,
+                                                             subrun_range, stream_ids)
+    out: List[Optional[dict]] = [None if c.fixed_price is None else _policy_result(c, hi - lo, None)
+                                 for c in plans]
+    for members in by_steps.values():
+        r = simulate_policy([plans[k] for k in members], [policies[k] for k in members], hi - lo,
+                            cfg.antithetic, engine=engine, seed=cfg.seed,
+                            stream_ids=[ids[k] for k in members], subrun_first=lo)
+        for row, k in enumerate(members):
+            out[k] = _policy_result(plans[k], hi - lo, r["stats"][row])
+    return out  # type: ignore[return-value]
+
+
+def price_policy_mc(contract: LsmContract, policy: ExercisePolicy, *, n_subruns: int = 32,
+                    antithetic: bool = True, seed: int = 42, stream_id: int = 0,
+                    engine: str = "hip") -> Dict[str, object]:
+    """The lower bound of one contract under `policy`: mc_policy_batch's dict
+    without the merging sums."""
+    cfg = LsmConfig(n_subruns=int(n_subruns), antithetic=bool(antithetic), seed=int(seed))
+    res = mc_policy_batch([contract], [policy], cfg, engine=engine, stream_ids=[stream_id])[0]
+    res.pop("sum_mean")
+    res.pop("sum_mean2")
+    return res
+
+
+def mc_policy_bounds_batch(contracts: Sequence[LsmContract], policies: Sequence[ExercisePolicy],
+                           cfg: LsmConfig = LsmConfig(), dual: DualConfig = DualConfig(), *,
+                           engine: str = "hip", stream_ids: Optional[Sequence[int]] = None,
+                           subrun_range: Optional[range] = None) -> List[dict]:
+    """Lower and upper bound of many contracts under given policies: per
+    distinct step count one lower-bound launch and one dual launch.  Results:
+    mc_policy_batch's dict plus what mc_american_bounds_batch adds (gap,
+    gap_stderr, upper, upper_stderr, n_outer, n_inner, sum_gap, sum_gap2,
+    dual_min_margin, inner_paths); `brackets` takes them as they are."""
+    plans, policies, lo, hi, ids, by_steps = _policy_batches(contracts, policies, cfg,
+                                                             subrun_range, stream_ids)
+    for c in plans:
+        _check_dual_contract(c)
+    _check_dual_sizes(dual.n_outer, dual.n_inner, bool(cfg.antithetic))
+    out: List[Optional[dict]] = [
+        None if c.fixed_price is None
+        else _bounds_result(_policy_result(c, hi - lo, None), dual, None) for c in plans]
+    for members in by_steps.values():
+        group, pols = [plans[k] for k in members], [policies[k] for k in members]
+        kw = dict(engine=engine, seed=cfg.seed, stream_ids=[ids[k] for k in members],
+                  subrun_first=lo)
+        r = simulate_policy(group, pols, hi - lo, cfg.antithetic, **kw)
+        d = simulate_policy_dual(group, pols, hi - lo, dual.n_outer, dual.n_inner,
+                                 cfg.antithetic, **kw)
+        for row, k in enumerate(members):
+            out[k] = _bounds_result(_policy_result(plans[k], hi - lo, r["stats"][row]), dual,
+                                    d["stats"][row])
+    return out  # type: ignore[return-value]
+
+
+def price_policy_mc_bounds(contract: LsmContract, policy: ExercisePolicy, *, n_subruns: int = 32,
+                           antithetic: bool = True, seed: int = 42, stream_id: int = 0,
+                           n_outer: int = 8, n_inner: int = 2048,
+                           engine: str = "hip") -> Dict[str, object]:
+    """Lower and upper bound of one contract under `policy`."""
+    cfg = LsmConfig(n_subruns=int(n_subruns), antithetic=bool(antithetic), seed=int(seed))
+    return mc_policy_bounds_batch([contract], [policy], cfg,
+                                  DualConfig(int(n_outer), int(n_inner)), engine=engine,
+                                  stream_ids=[stream_id])[0]

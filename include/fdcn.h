@@ -979,6 +979,110 @@ int fdcn_mc_lsm_dual_plan(int32_t n_steps, int32_t G, int32_t antithetic, int32_
                           int32_t n_inner, int64_t* ws_bytes_per_contract,
                           int64_t* gap_per_contract, int64_t* cont_per_contract);
 
+/* ---- Monte Carlo bounds under a given exercise table (csrc/fdcn_mc_policy.hip,
+ * csrc/fdcn_mc_policy.h).  The least-squares Monte Carlo fits its stopping
+ * rule; here the rule is an input, for instance the exercise boundary of a
+ * Bermudan FD pricer (mc_american.policy_from_pricer).  Any rule gives a lower
+ * bound and any rule gives a dual upper bound, so a wrong table shows as a low
+ * lower bound and a wide gap, never as agreement.  Additive: FDCN_ABI_VERSION
+ * is still 8.
+ *   params, flags, step                 as in fdcn_mc_lsm_batch
+ *   policy [B][n_steps][FDCN_POLICY_NCOL]  row m - 1 is step m: X_LO_m, X_HI_m,
+ *                                       a band in the log-spot.  Per contract,
+ *                                       not per sub-run.
+ * The table rule replaces phase C's fitted rule.  It stops a path at step m
+ * when all of these hold: m < n_steps; EXERCISE_m != 0; the path is eligible;
+ * X_LO_m <= x <= X_HI_m, both ends inclusive; phi > 0.  +-inf are legal
+ * entries, X_LO_m > X_HI_m means never at that step, and a row on a step
+ * without an EXERCISE flag is ignored.  Everything else is phase C word for
+ * word: the move x += DRIFT_m + DIFF_m * z_m; on a knock-out a monitored
+ * breach is checked first and pays max(phi, REBATE_m); a knock-in path is
+ * eligible from its hit step on, that step included; maturity always stops;
+ * the value is the cashflow times DF_END_m; every operation is rounded
+ * separately.  The band is compared in x, so exp(x) is evaluated only on a
+ * MONITOR step of a barrier contract, for an in-band decision and at maturity.
+ * A rule decision is taken for every path that is alive and eligible at an
+ * EXERCISE step m < n_steps, whatever its phi (phi is read in band only);
+ * MIN_MARGIN is the smallest distance |x - X_LO_m|, |x - X_HI_m| to a finite
+ * entry over those decisions: no decision of a run can flip under a
+ * perturbation of x smaller than it.
+ * Cash dividends are out of scope: there is no `div` input.
+ *
+ * Lower bound, fdcn_mc_policy_batch.  The paths are the LSM's price set:
+ * counter word 3 = 2 * stream id + 1, the observation mapping, the antithetic
+ * pairing by slot parity, FDCN_LSM_SUBRUN paths per sub-run, one workgroup of
+ * 256 threads per (contract, sub-run) and obs_first as in fdcn_mc_lsm_batch,
+ * so values_out of the two entries pair path for path.  The reduction is the
+ * LSM's too: per thread in slot order, the fixed tree v[t] + v[t + off], off =
+ * 128 .. 1, one partial per sub-run, added in sub-run order by a second kernel;
+ * no floating-point atomics.  With a table that never stops, PRICE, STDERR,
+ * SUM, SUM2 and values_out are those of fdcn_mc_lsm_batch on the contract
+ * with its EXERCISE flags cleared, bit for bit.
+ *   stats [B][FDCN_POLICY_NSTAT]        see enum fdcn_policy_stat
+ *   values_out [B][G * FDCN_LSM_SUBRUN] value per path (NULL: none)
+ * Validation (before any device call; FDCN_EINVAL): all of fdcn_mc_lsm_batch,
+ * NULL policy, and, host entry only, a NaN in policy. */
+#define FDCN_POLICY_NCOL 2
+enum fdcn_policy_col {
+  FDCN_POLICY_X_LO = 0, /* stop only where x >= X_LO_m (-inf: no lower end)    */
+  FDCN_POLICY_X_HI      /* stop only where x <= X_HI_m (+inf: no upper end)    */
+};
+#define FDCN_POLICY_NSTAT 6
+enum fdcn_policy_stat {
+  FDCN_POLICY_O_PRICE = 0,  /* mean of the sub-run means                          */
+  FDCN_POLICY_O_STDERR,     /* their sample standard deviation / sqrt(G); 0: G = 1 */
+  FDCN_POLICY_O_SUM,        /* sum of the sub-run means (merging)                 */
+  FDCN_POLICY_O_SUM2,       /* sum of their squares                               */
+  FDCN_POLICY_O_MIN_MARGIN, /* min distance of x to a finite X_LO_m / X_HI_m over
+                               the rule decisions taken; +inf if none            */
+  FDCN_POLICY_O_EXERCISED   /* paths the rule stopped (an exact integer)          */
+};
+/* Host pointers; copies in and out on the calling thread's stream and waits. */
+int fdcn_mc_policy_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                         const double* params, const int32_t* flags, const double* step,
+                         const double* policy, uint64_t seed, int64_t obs_first, double* stats,
+                         double* values_out);
+/* Device pointers, asynchronous on `stream`, no host sync; `workspace` as in
+ * fdcn_mc_lsm_batch_dev, sized by fdcn_mc_policy_plan, or NULL.  The contents
+ * of the arrays are not checked here. */
+int fdcn_mc_policy_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                             const double* params, const int32_t* flags, const double* step,
+                             const double* policy, uint64_t seed, int64_t obs_first,
+                             double* stats, double* values_out, double* workspace,
+                             int64_t workspace_bytes, void* stream);
+/* Geometry of a launch: observations per sub-run, workspace bytes per
+ * contract, doubles per contract of values_out.  Any output pointer may be
+ * NULL.  Host only. */
+int fdcn_mc_policy_plan(int32_t n_steps, int32_t G, int32_t antithetic, int32_t* obs_per_subrun,
+                        int64_t* ws_bytes_per_contract, int64_t* values_per_contract);
+
+/* Upper bound, fdcn_mc_policy_dual_batch: the contract of
+ * fdcn_mc_lsm_dual_batch with policy [B][n_steps][FDCN_POLICY_NCOL] in the
+ * place of coef.  The outer and inner streams (bit 31 words), the observation
+ * packing, the limits of n_outer and n_inner, FDCN_DUAL_NSTAT, gap_out and
+ * cont_out are unchanged.  A candidate arises at every EXERCISE step m <
+ * n_steps at which the outer path is eligible with phi > 0; "the rule stops
+ * at m" is X_LO_m <= x <= X_HI_m, for the outer and the inner walks alike.
+ * MIN_MARGIN is the x-distance defined above, over the decisions of outer and
+ * inner paths.  With a table that never stops, every output is that of
+ * fdcn_mc_lsm_dual_batch with an all-zero coef, bit for bit.
+ * Validation: that of fdcn_mc_lsm_dual_batch with policy in the place of coef;
+ * host entry only, a NaN in policy. */
+int fdcn_mc_policy_dual_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                              int32_t n_outer, int32_t n_inner, const double* params,
+                              const int32_t* flags, const double* step, const double* policy,
+                              uint64_t seed, int64_t subrun_first, double* stats,
+                              double* gap_out, double* cont_out);
+int fdcn_mc_policy_dual_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                                  int32_t n_outer, int32_t n_inner, const double* params,
+                                  const int32_t* flags, const double* step,
+                                  const double* policy, uint64_t seed, int64_t subrun_first,
+                                  double* stats, double* gap_out, double* cont_out,
+                                  double* workspace, int64_t workspace_bytes, void* stream);
+int fdcn_mc_policy_dual_plan(int32_t n_steps, int32_t G, int32_t antithetic, int32_t n_outer,
+                             int32_t n_inner, int64_t* ws_bytes_per_contract,
+                             int64_t* gap_per_contract, int64_t* cont_per_contract);
+
 /* ---- host-side plan helpers (no device) -------------------------------- */
 /* Uniform log grid of the pricers' _build_log_grid
  * (discrete_barrier_fdm_pricer.py:342-364, fd_american_equity.py:363-384):
