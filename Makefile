@@ -41,7 +41,7 @@ CSRC := finite_difference_amd/csrc
 HOST_SRCS := $(CSRC)/fdcn_host.hip $(CSRC)/fdcn_plan.hip
 HDRS := include/fdcn.h include/fdcn_diag.h $(CSRC)/fdcn_shared.h $(CSRC)/fdcn_session_book.h \
         $(CSRC)/fdcn_host_call.h $(CSRC)/fdcn_philox.h $(CSRC)/fdcn_mc_path.h \
-        $(CSRC)/fdcn_qmc_table.h $(CSRC)/fdcn_mc_policy.h
+        $(CSRC)/fdcn_qmc_table.h $(CSRC)/fdcn_mc_policy.h $(CSRC)/fdcn_mc_div.h
 DEV_OBJS := build/obj/fdcn_kernels.o build/obj/fdcn_analytic.o build/obj/fdcn_session.o \
             build/obj/fdcn_vc.o build/obj/fdcn_mc.o build/obj/fdcn_mc_bgk.o \
             build/obj/fdcn_mc_lsm.o build/obj/fdcn_mc_qmc.o \

@@ -54,6 +54,9 @@ EXPORTED = ("fdcn_cn_batch", "fdcn_it_batch", "fdcn_cn_batch_dev", "fdcn_it_batc
             "fdcn_mc_policy_batch", "fdcn_mc_policy_batch_dev", "fdcn_mc_policy_plan",
             "fdcn_mc_policy_dual_batch", "fdcn_mc_policy_dual_batch_dev",
             "fdcn_mc_policy_dual_plan",
+            "fdcn_mc_lsm_dual_div_batch", "fdcn_mc_lsm_dual_div_batch_dev",
+            "fdcn_mc_policy_div_batch", "fdcn_mc_policy_div_batch_dev",
+            "fdcn_mc_policy_dual_div_batch", "fdcn_mc_policy_dual_div_batch_dev",
             "fdcn_mc_qmc_batch", "fdcn_mc_qmc_batch_dev", "fdcn_mc_qmc_plan")
 # include/fdcn_diag.h: test / tuning entry points, not the product boundary
 DIAG_EXPORTED = ("fdcn_force_variant", "fdcn_forced_variant", "fdcn_variant_name",
@@ -341,6 +344,26 @@ def lib() -> ctypes.CDLL:
             L.fdcn_mc_policy_dual_batch_dev.argtypes = L.fdcn_mc_lsm_dual_batch_dev.argtypes
             L.fdcn_mc_policy_dual_plan.restype = _I
             L.fdcn_mc_policy_dual_plan.argtypes = L.fdcn_mc_lsm_dual_plan.argtypes
+            # the div forms: one more pointer after `step`
+            L.fdcn_mc_lsm_dual_div_batch.restype = _I
+            L.fdcn_mc_lsm_dual_div_batch.argtypes = [_I, _I, _I, _I, _I, _I, _V, _V, _V, _V, _V,
+                                                     ctypes.c_uint64, _I64, _V, _V, _V]
+            L.fdcn_mc_lsm_dual_div_batch_dev.restype = _I
+            L.fdcn_mc_lsm_dual_div_batch_dev.argtypes = [_I, _I, _I, _I, _I, _I, _V, _V, _V, _V,
+                                                         _V, ctypes.c_uint64, _I64, _V, _V, _V,
+                                                         _V, _I64, _V]
+            L.fdcn_mc_policy_div_batch.restype = _I
+            L.fdcn_mc_policy_div_batch.argtypes = [_I, _I, _I, _I, _V, _V, _V, _V, _V,
+                                                   ctypes.c_uint64, _I64, _V, _V]
+            L.fdcn_mc_policy_div_batch_dev.restype = _I
+            L.fdcn_mc_policy_div_batch_dev.argtypes = [_I, _I, _I, _I, _V, _V, _V, _V, _V,
+                                                       ctypes.c_uint64, _I64, _V, _V, _V, _I64,
+                                                       _V]
+            L.fdcn_mc_policy_dual_div_batch.restype = _I
+            L.fdcn_mc_policy_dual_div_batch.argtypes = L.fdcn_mc_lsm_dual_div_batch.argtypes
+            L.fdcn_mc_policy_dual_div_batch_dev.restype = _I
+            L.fdcn_mc_policy_dual_div_batch_dev.argtypes = \
+                L.fdcn_mc_lsm_dual_div_batch_dev.argtypes
             L.fdcn_mc_normals.restype = _I
             L.fdcn_mc_normals.argtypes = [_I64, _I, ctypes.c_uint64, _I, _I64, _V]
             L.fdcn_mc_qmc_batch.restype = _I
@@ -1022,13 +1045,23 @@ def mc_dual_plan(n_steps: int, G: int, antithetic: bool, n_outer: int, n_inner: 
                 cont_per_contract=nc.value)
 
 
+def _div_rows(who: str, div, B: int, n_steps: int) -> np.ndarray:
+    if div is None:
+        raise ValueError(f"{who}: div is missing")
+    D = _f64(div)
+    if D.shape != (B, n_steps):
+        raise ValueError(f"{who}: div [B, n_steps]")
+    return D
+
+
 def mc_dual_batch(params, flags, step, coef, n_outer: int, n_inner: int, antithetic: bool, *,
                   seed: int = 0, subrun_first: int = 0, want_gap: bool = False,
-                  want_cont: bool = False):
+                  want_cont: bool = False, div=None):
     """fdcn_mc_lsm_dual_batch on host arrays -> (stats [B, DUAL_NSTAT], gap
     [B, G * n_outer] or None, cont [B, G * n_outer, n_steps] or None).  params
     [B, LSM_NPARAM], flags [B, LSM_NFLAG], step [B, n_steps, LSM_NSTEP], coef
-    [B, G, n_steps, LSM_NCOEF] (mc_lsm_batch's coefficient dump)."""
+    [B, G, n_steps, LSM_NCOEF] (mc_lsm_batch's coefficient dump).  With div
+    [B, n_steps] (cash dividends on the path): fdcn_mc_lsm_dual_div_batch."""
     require_device()
     P = _f64(params).reshape(-1, LSM_NPARAM)
     F = _i32(flags).reshape(-1, LSM_NFLAG)
@@ -1045,12 +1078,25 @@ def mc_dual_batch(params, flags, step, coef, n_outer: int, n_inner: int, antithe
     rows = G * max(n_outer, 0)
     gap = np.empty((B, rows), dtype=np.float64) if want_gap else None
     cont = np.empty((B, rows, n_steps), dtype=np.float64) if want_cont else None
-    _check(lib().fdcn_mc_lsm_dual_batch(
-        B, n_steps, G, 1 if antithetic else 0, n_outer, int(n_inner), P.ctypes.data,
-        F.ctypes.data, S.ctypes.data, C.ctypes.data, int(seed) & (2 ** 64 - 1),
-        int(subrun_first), stats.ctypes.data, gap.ctypes.data if want_gap else None,
-        cont.ctypes.data if want_cont else None))
+    tail = (C.ctypes.data, int(seed) & (2 ** 64 - 1), int(subrun_first), stats.ctypes.data,
+            gap.ctypes.data if want_gap else None, cont.ctypes.data if want_cont else None)
+    head = (B, n_steps, G, 1 if antithetic else 0, n_outer, int(n_inner), P.ctypes.data,
+            F.ctypes.data, S.ctypes.data)
+    if div is None:
+        _check(lib().fdcn_mc_lsm_dual_batch(*head, *tail))
+    else:
+        D = _div_rows("mc_dual_batch", div, B, n_steps)
+        _check(lib().fdcn_mc_lsm_dual_div_batch(*head, D.ctypes.data, *tail))
     return stats, gap, cont
+
+
+def mc_dual_div_batch(params, flags, step, div, coef, n_outer: int, n_inner: int,
+                      antithetic: bool, **kw):
+    """fdcn_mc_lsm_dual_div_batch on host arrays: mc_dual_batch with the dividend
+    rows div [B, n_steps] (an all-zero div still takes the div entry)."""
+    if div is None:
+        raise ValueError("mc_dual_div_batch: div is missing")
+    return mc_dual_batch(params, flags, step, coef, n_outer, n_inner, antithetic, div=div, **kw)
 
 
 def mc_dual_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, n_outer: int, n_inner: int,
@@ -1064,6 +1110,21 @@ def mc_dual_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, n_outer: i
         int(B), int(n_steps), int(G), 1 if antithetic else 0, int(n_outer), int(n_inner),
         params_ptr, flags_ptr, step_ptr, coef_ptr, int(seed) & (2 ** 64 - 1), int(subrun_first),
         stats_ptr, gap_ptr, cont_ptr, workspace_ptr, int(workspace_bytes), stream_ptr))
+
+
+def mc_dual_div_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, n_outer: int,
+                          n_inner: int, params_ptr: int, flags_ptr: int, step_ptr: int,
+                          div_ptr: int, coef_ptr: int, seed: int, subrun_first: int,
+                          stats_ptr: int, gap_ptr: Optional[int], cont_ptr: Optional[int],
+                          workspace_ptr: Optional[int], workspace_bytes: int,
+                          stream_ptr: Optional[int]) -> None:
+    """fdcn_mc_lsm_dual_div_batch_dev: mc_dual_batch_dev with the dividend rows
+    div [B, n_steps] on the device."""
+    _check(lib().fdcn_mc_lsm_dual_div_batch_dev(
+        int(B), int(n_steps), int(G), 1 if antithetic else 0, int(n_outer), int(n_inner),
+        params_ptr, flags_ptr, step_ptr, div_ptr, coef_ptr, int(seed) & (2 ** 64 - 1),
+        int(subrun_first), stats_ptr, gap_ptr, cont_ptr, workspace_ptr, int(workspace_bytes),
+        stream_ptr))
 
 
 def mc_policy_plan(n_steps: int, G: int, antithetic: bool) -> dict:
@@ -1092,20 +1153,33 @@ def _policy_arrays(who: str, params, flags, step, policy):
 
 
 def mc_policy_batch(params, flags, step, policy, G: int, antithetic: bool, *, seed: int = 0,
-                    obs_first: int = 0, want_values: bool = False):
+                    obs_first: int = 0, want_values: bool = False, div=None):
     """fdcn_mc_policy_batch on host arrays -> (stats [B, POLICY_NSTAT], values
     [B, G * LSM_SUBRUN] or None).  params, flags, step as mc_lsm_batch; policy
-    [B, n_steps, POLICY_NCOL]."""
+    [B, n_steps, POLICY_NCOL].  With div [B, n_steps] (cash dividends on the
+    path): fdcn_mc_policy_div_batch."""
     require_device()
     P, F, S, T = _policy_arrays("mc_policy_batch", params, flags, step, policy)
     B, n_steps, G = P.shape[0], S.shape[1], int(G)
     stats = np.empty((B, POLICY_NSTAT), dtype=np.float64)
     val = np.empty((B, max(G, 0) * LSM_SUBRUN), dtype=np.float64) if want_values else None
-    _check(lib().fdcn_mc_policy_batch(
-        B, n_steps, G, 1 if antithetic else 0, P.ctypes.data, F.ctypes.data, S.ctypes.data,
-        T.ctypes.data, int(seed) & (2 ** 64 - 1), int(obs_first), stats.ctypes.data,
-        val.ctypes.data if want_values else None))
+    head = (B, n_steps, G, 1 if antithetic else 0, P.ctypes.data, F.ctypes.data, S.ctypes.data)
+    tail = (T.ctypes.data, int(seed) & (2 ** 64 - 1), int(obs_first), stats.ctypes.data,
+            val.ctypes.data if want_values else None)
+    if div is None:
+        _check(lib().fdcn_mc_policy_batch(*head, *tail))
+    else:
+        D = _div_rows("mc_policy_batch", div, B, n_steps)
+        _check(lib().fdcn_mc_policy_div_batch(*head, D.ctypes.data, *tail))
     return stats, val
+
+
+def mc_policy_div_batch(params, flags, step, div, policy, G: int, antithetic: bool, **kw):
+    """fdcn_mc_policy_div_batch on host arrays: mc_policy_batch with the dividend
+    rows div [B, n_steps] (an all-zero div still takes the div entry)."""
+    if div is None:
+        raise ValueError("mc_policy_div_batch: div is missing")
+    return mc_policy_batch(params, flags, step, policy, G, antithetic, div=div, **kw)
 
 
 def mc_policy_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, params_ptr: int,
@@ -1118,6 +1192,19 @@ def mc_policy_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, params_p
     _check(lib().fdcn_mc_policy_batch_dev(
         int(B), int(n_steps), int(G), 1 if antithetic else 0, params_ptr, flags_ptr, step_ptr,
         policy_ptr, int(seed) & (2 ** 64 - 1), int(obs_first), stats_ptr, values_ptr,
+        workspace_ptr, int(workspace_bytes), stream_ptr))
+
+
+def mc_policy_div_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, params_ptr: int,
+                            flags_ptr: int, step_ptr: int, div_ptr: int, policy_ptr: int,
+                            seed: int, obs_first: int, stats_ptr: int,
+                            values_ptr: Optional[int], workspace_ptr: Optional[int],
+                            workspace_bytes: int, stream_ptr: Optional[int]) -> None:
+    """fdcn_mc_policy_div_batch_dev: mc_policy_batch_dev with the dividend rows
+    div [B, n_steps] on the device."""
+    _check(lib().fdcn_mc_policy_div_batch_dev(
+        int(B), int(n_steps), int(G), 1 if antithetic else 0, params_ptr, flags_ptr, step_ptr,
+        div_ptr, policy_ptr, int(seed) & (2 ** 64 - 1), int(obs_first), stats_ptr, values_ptr,
         workspace_ptr, int(workspace_bytes), stream_ptr))
 
 
@@ -1135,10 +1222,11 @@ def mc_policy_dual_plan(n_steps: int, G: int, antithetic: bool, n_outer: int,
 
 def mc_policy_dual_batch(params, flags, step, policy, G: int, n_outer: int, n_inner: int,
                          antithetic: bool, *, seed: int = 0, subrun_first: int = 0,
-                         want_gap: bool = False, want_cont: bool = False):
+                         want_gap: bool = False, want_cont: bool = False, div=None):
     """fdcn_mc_policy_dual_batch on host arrays -> (stats [B, DUAL_NSTAT], gap
     [B, G * n_outer] or None, cont [B, G * n_outer, n_steps] or None); policy
-    [B, n_steps, POLICY_NCOL]."""
+    [B, n_steps, POLICY_NCOL].  With div [B, n_steps] (cash dividends on the
+    path): fdcn_mc_policy_dual_div_batch."""
     require_device()
     P, F, S, T = _policy_arrays("mc_policy_dual_batch", params, flags, step, policy)
     B, n_steps, G, n_outer = P.shape[0], S.shape[1], int(G), int(n_outer)
@@ -1146,12 +1234,26 @@ def mc_policy_dual_batch(params, flags, step, policy, G: int, n_outer: int, n_in
     rows = max(G, 0) * max(n_outer, 0)
     gap = np.empty((B, rows), dtype=np.float64) if want_gap else None
     cont = np.empty((B, rows, n_steps), dtype=np.float64) if want_cont else None
-    _check(lib().fdcn_mc_policy_dual_batch(
-        B, n_steps, G, 1 if antithetic else 0, n_outer, int(n_inner), P.ctypes.data,
-        F.ctypes.data, S.ctypes.data, T.ctypes.data, int(seed) & (2 ** 64 - 1),
-        int(subrun_first), stats.ctypes.data, gap.ctypes.data if want_gap else None,
-        cont.ctypes.data if want_cont else None))
+    head = (B, n_steps, G, 1 if antithetic else 0, n_outer, int(n_inner), P.ctypes.data,
+            F.ctypes.data, S.ctypes.data)
+    tail = (T.ctypes.data, int(seed) & (2 ** 64 - 1), int(subrun_first), stats.ctypes.data,
+            gap.ctypes.data if want_gap else None, cont.ctypes.data if want_cont else None)
+    if div is None:
+        _check(lib().fdcn_mc_policy_dual_batch(*head, *tail))
+    else:
+        D = _div_rows("mc_policy_dual_batch", div, B, n_steps)
+        _check(lib().fdcn_mc_policy_dual_div_batch(*head, D.ctypes.data, *tail))
     return stats, gap, cont
+
+
+def mc_policy_dual_div_batch(params, flags, step, div, policy, G: int, n_outer: int,
+                             n_inner: int, antithetic: bool, **kw):
+    """fdcn_mc_policy_dual_div_batch on host arrays: mc_policy_dual_batch with the
+    dividend rows div [B, n_steps] (an all-zero div still takes the div entry)."""
+    if div is None:
+        raise ValueError("mc_policy_dual_div_batch: div is missing")
+    return mc_policy_dual_batch(params, flags, step, policy, G, n_outer, n_inner, antithetic,
+                                div=div, **kw)
 
 
 def mc_policy_dual_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, n_outer: int,
@@ -1165,5 +1267,20 @@ def mc_policy_dual_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, n_o
     _check(lib().fdcn_mc_policy_dual_batch_dev(
         int(B), int(n_steps), int(G), 1 if antithetic else 0, int(n_outer), int(n_inner),
         params_ptr, flags_ptr, step_ptr, policy_ptr, int(seed) & (2 ** 64 - 1),
+        int(subrun_first), stats_ptr, gap_ptr, cont_ptr, workspace_ptr, int(workspace_bytes),
+        stream_ptr))
+
+
+def mc_policy_dual_div_batch_dev(B: int, n_steps: int, G: int, antithetic: bool, n_outer: int,
+                                 n_inner: int, params_ptr: int, flags_ptr: int, step_ptr: int,
+                                 div_ptr: int, policy_ptr: int, seed: int, subrun_first: int,
+                                 stats_ptr: int, gap_ptr: Optional[int],
+                                 cont_ptr: Optional[int], workspace_ptr: Optional[int],
+                                 workspace_bytes: int, stream_ptr: Optional[int]) -> None:
+    """fdcn_mc_policy_dual_div_batch_dev: mc_policy_dual_batch_dev with the
+    dividend rows div [B, n_steps] on the device."""
+    _check(lib().fdcn_mc_policy_dual_div_batch_dev(
+        int(B), int(n_steps), int(G), 1 if antithetic else 0, int(n_outer), int(n_inner),
+        params_ptr, flags_ptr, step_ptr, div_ptr, policy_ptr, int(seed) & (2 ** 64 - 1),
         int(subrun_first), stats_ptr, gap_ptr, cont_ptr, workspace_ptr, int(workspace_bytes),
         stream_ptr))

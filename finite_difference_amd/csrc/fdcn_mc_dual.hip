@@ -9,7 +9,8 @@
 // rules and the Philox mapping are the contract of include/fdcn.h
 // (fdcn_mc_lsm_dual_batch).
 //
-//   dual_kernel<ANTI>     one workgroup of 256 threads = one sub-run of one
+//   dual_kernel<ANTI, DIV>
+//                         one workgroup of 256 threads = one sub-run of one
 //                         contract.  The outer path is walked by every thread
 //                         alike (no thread index enters it, so its branches
 //                         are uniform and the barriers inside them are safe);
@@ -31,6 +32,13 @@
 // atomics; multiply and add are rounded separately (contraction off), so the
 // NumPy host engine (mc_american.host_dual_subruns) differs only through exp /
 // log / the normals and not through summation order.
+//
+// DIV = true (fdcn_mc_lsm_dual_div_batch): a step may pay a cash dividend D_m,
+// read from the row div[b][n_steps] with scalar loads like the step rows (both
+// walks index it by their loop counter), so the branch on D_m != 0 is uniform.
+// Both walks only go forward: after the move the spot goes through g
+// (fdcn_mc_div.h), then the step's events see the ex-dividend spot.  No per-path
+// state is added; DIV = false is the kernel without any of it.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -43,6 +51,8 @@
 
 #pragma clang fp contract(off)
 
+#include "fdcn_mc_div.h"
+
 namespace {
 
 constexpr int kThreads = 256;
@@ -54,6 +64,8 @@ static_assert((1 << kObsBits) == FDCN_DUAL_MAX_INNER, "fdcn.h");
 static_assert((1 << kStepBits) == FDCN_LSM_MAX_STEPS, "fdcn.h");
 static_assert((1 << kOuterBits) == FDCN_DUAL_MAX_OUTER, "fdcn.h");
 
+using fdcn_div::div_at;
+using fdcn_div::div_forward;
 using fdcn_philox::normal_pair;
 
 struct DualArgs {
@@ -108,14 +120,17 @@ __device__ __forceinline__ double block_reduce(double* sh, double v, int tid) {
   return uniform(sh[kThreads]);
 }
 
-// One step of an inner path: phase C of fdcn_mc_lsm.hip on step row r, fit cc.
+// One step of an inner path: phase C of fdcn_mc_lsm.hip on step row r, fit cc,
+// dividend dv of the step (uniform; 0.0 for none, and in the instances without
+// dividends a constant, so the map folds away).
 __device__ __forceinline__ void inner_step(const Contract& c, const double* r, const double* cc,
-                                           bool last, bool use_mon, double z, double& x,
-                                           bool& done, bool& in, double& val, double& margin,
-                                           uint64_t& walked) {
+                                           bool last, bool use_mon, double z, double dv,
+                                           double& x, bool& done, bool& in, double& val,
+                                           double& margin, uint64_t& walked) {
   if (done) return;
   ++walked;
   x += r[FDCN_LSM_S_DRIFT] + r[FDCN_LSM_S_DIFF] * z;
+  if (dv != 0.0) x = div_forward(x, dv);  // a step without a flag still pays
   const bool mon = use_mon && r[FDCN_LSM_S_MONITOR] != 0.0;
   const bool fitted = !last && r[FDCN_LSM_S_EXERCISE] != 0.0 && cc[4] != 0.0;
   if (!(mon || fitted || last)) return;
@@ -145,12 +160,15 @@ __device__ __forceinline__ void inner_step(const Contract& c, const double* r, c
 }
 
 // 4 waves per SIMD: the antithetic instance needs 131 VGPRs without the bound,
-// 128 with it, and neither spills.
-template <bool ANTI>
-__global__ void __launch_bounds__(kThreads, 4)
+// 128 with it, and neither spills.  The antithetic instance with dividends
+// spills under that bound (the map's exp and log are live beside two paths), so
+// it alone is bound to 3 waves.
+template <bool ANTI, bool DIV>
+__global__ void __launch_bounds__(kThreads, (ANTI && DIV) ? 3 : 4)
 dual_kernel(DualArgs a, const double* __restrict__ params, const int32_t* __restrict__ flags,
             const double* __restrict__ step, const double* __restrict__ coef,
-            double* __restrict__ ws, double* __restrict__ gap_out, double* __restrict__ cont_out) {
+            double* __restrict__ ws, double* __restrict__ gap_out, double* __restrict__ cont_out,
+            const double* __restrict__ div) {
   const int b = blockIdx.x / a.G;  // contract
   const int g = blockIdx.x % a.G;  // sub-run
   const int tid = threadIdx.x;
@@ -159,6 +177,7 @@ dual_kernel(DualArgs a, const double* __restrict__ params, const int32_t* __rest
   const int32_t* F = flags + (size_t)b * FDCN_LSM_NFLAG;
   const double* S = step + (size_t)b * M * FDCN_LSM_NSTEP;
   const double* C = coef + ((size_t)b * a.G + g) * (size_t)M * FDCN_LSM_NCOEF;
+  const double* D = DIV ? div + (size_t)b * M : nullptr;  // uniform, like S
   Contract c;
   c.strike = P[FDCN_LSM_P_STRIKE];
   c.lower = P[FDCN_LSM_P_LOWER];
@@ -189,7 +208,7 @@ dual_kernel(DualArgs a, const double* __restrict__ params, const int32_t* __rest
     const uint64_t obs_outer = gs * (uint64_t)a.n_outer + (uint64_t)p;
     const size_t row_out = ((size_t)b * a.G + g) * (size_t)a.n_outer + (size_t)p;
     double* cont = cont_out ? cont_out + row_out * (size_t)M : nullptr;
-    double x = x0, r = 0.0, D = -INFINITY;
+    double x = x0, r = 0.0, gap = -INFINITY;
     bool in = false;
     double z0 = 0.0, z1 = 0.0;
     int i = 0;
@@ -198,6 +217,10 @@ dual_kernel(DualArgs a, const double* __restrict__ params, const int32_t* __rest
       const double* row = S + (size_t)i * FDCN_LSM_NSTEP;
       const double* cc = C + (size_t)i * FDCN_LSM_NCOEF;
       x += row[FDCN_LSM_S_DRIFT] + row[FDCN_LSM_S_DIFF] * ((i & 1) ? z1 : z0);
+      if (DIV) {  // the dividend, then the step's events on the ex-dividend spot
+        const double dv = div_at(D, i);
+        if (dv != 0.0) x = div_forward(x, dv);
+      }
       const bool last = i + 1 == M;
       const bool mon = use_mon && row[FDCN_LSM_S_MONITOR] != 0.0;
       const bool ex = !last && row[FDCN_LSM_S_EXERCISE] != 0.0;
@@ -230,9 +253,11 @@ dual_kernel(DualArgs a, const double* __restrict__ params, const int32_t* __rest
                 const double* ri = S + (size_t)ii * FDCN_LSM_NSTEP;
                 const double* ci = C + (size_t)ii * FDCN_LSM_NCOEF;
                 const bool li = ii + 1 == M;
-                inner_step(c, ri, ci, li, use_mon, zz[hf], xa, da, ia, va, margin, walked);
+                const double dv = DIV ? div_at(D, ii) : 0.0;
+                inner_step(c, ri, ci, li, use_mon, zz[hf], dv, xa, da, ia, va, margin, walked);
                 if (ANTI)
-                  inner_step(c, ri, ci, li, use_mon, -zz[hf], xb, db, ib, vb, margin, walked);
+                  inner_step(c, ri, ci, li, use_mon, -zz[hf], dv, xb, db, ib, vb, margin,
+                             walked);
               }
               if (da && db) break;
             }
@@ -251,24 +276,24 @@ dual_kernel(DualArgs a, const double* __restrict__ params, const int32_t* __rest
             stops = phi > fit;
           }
           if (stops) {
-            D = fmax(D, 0.0 - r);
+            gap = fmax(gap, 0.0 - r);
             r += Z - chat;
           } else {
-            D = fmax(D, (Z - chat) - r);
+            gap = fmax(gap, (Z - chat) - r);
           }
         }
       }
       if (cont && tid == 0) cont[i] = chat;
       if (forced) {
-        D = fmax(D, 0.0 - r);
+        gap = fmax(gap, 0.0 - r);
         break;
       }
     }
     // the steps after a knock-out: no inner simulation
     if (cont)
       for (int k = i + 1 + tid; k < M; k += kThreads) cont[k] = 0.0;
-    if (gap_out && tid == 0) gap_out[row_out] = D;
-    sum_d += D;
+    if (gap_out && tid == 0) gap_out[row_out] = gap;
+    sum_d += gap;
   }
 
   const double tot_margin = block_reduce<true>(sh, margin, tid);
@@ -391,12 +416,27 @@ int check_contracts(int32_t B, int32_t n_steps, int32_t G, const double* params,
   return FDCN_OK;
 }
 
+// every dividend finite and >= 0 (a dividend on the last step is legal)
+int check_dividends(int32_t B, int32_t n_steps, const double* div) {
+  char msg[200];
+  for (int32_t b = 0; b < B; ++b)
+    for (int32_t m = 0; m < n_steps; ++m) {
+      const double d = div[(size_t)b * n_steps + m];
+      if (isfinite(d) && d >= 0.0) continue;
+      snprintf(msg, sizeof msg, "mc_lsm_dual_div_batch: contract %d: the dividend of step %d %s",
+               b, m + 1, isfinite(d) ? "is negative" : "is not finite");
+      return dfail(FDCN_EINVAL, msg);
+    }
+  return FDCN_OK;
+}
+
 int64_t ws_bytes(int32_t G) { return (int64_t)G * kWsRow * (int64_t)sizeof(double); }
 
 int launch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic, int32_t n_outer,
            int32_t n_inner, const double* params, const int32_t* flags, const double* step,
            const double* coef, uint64_t seed, int64_t subrun_first, double* stats,
-           double* gap_out, double* cont_out, double* workspace, hipStream_t stream) {
+           double* gap_out, double* cont_out, double* workspace, hipStream_t stream,
+           const double* div = nullptr) {
   DualArgs a;
   a.n_steps = n_steps;
   a.G = G;
@@ -405,9 +445,11 @@ int launch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic, int32_t n_
   a.subrun_first = subrun_first;
   a.seed = seed;
   const dim3 grid((uint32_t)((int64_t)B * G)), block(kThreads);
-  auto fn = antithetic ? dual_kernel<true> : dual_kernel<false>;
+  // the div entries always run a DIV instance, an all-zero row included
+  auto fn = div ? (antithetic ? dual_kernel<true, true> : dual_kernel<false, true>)
+                : (antithetic ? dual_kernel<true, false> : dual_kernel<false, false>);
   hipLaunchKernelGGL(fn, grid, block, 0, stream, a, params, flags, step, coef, workspace,
-                     gap_out, cont_out);
+                     gap_out, cont_out, div);
   if (hipGetLastError() != hipSuccess)
     return dfail(FDCN_EHIP, "mc_lsm_dual_batch: launch failed");
   hipLaunchKernelGGL(dual_finalize_kernel, dim3((B + kThreads - 1) / kThreads), block, 0, stream,
@@ -478,6 +520,60 @@ int fdcn_mc_lsm_dual_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antith
                   c.dev<int32_t>(rF), c.dev<double>(rS), c.dev<double>(rC), seed, subrun_first,
                   c.dev<double>(rO), c.dev<double>(rG), c.dev<double>(rY), c.dev<double>(rW),
                   stream);
+  });
+}
+
+int fdcn_mc_lsm_dual_div_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                                   int32_t n_outer, int32_t n_inner, const double* params,
+                                   const int32_t* flags, const double* step, const double* div,
+                                   const double* coef, uint64_t seed, int64_t subrun_first,
+                                   double* stats, double* gap_out, double* cont_out,
+                                   double* workspace, int64_t workspace_bytes, void* stream) {
+  int rc = check_sizes(B, n_steps, G, antithetic, n_outer, n_inner, subrun_first);
+  if (rc) return rc;
+  rc = check_pointers("mc_lsm_dual_div_batch_dev", params, flags, step, coef, stats);
+  if (rc) return rc;
+  if (!div) return dfail(FDCN_EINVAL, "mc_lsm_dual_div_batch_dev: div is NULL");
+  return fdcn_call::with_workspace<fdcn_internal::HipCall>(
+      "mc_lsm_dual_div_batch_dev", "this launch needs (fdcn_mc_lsm_dual_plan)", workspace,
+      workspace_bytes, ws_bytes(G) * B, (hipStream_t)stream, [&](void* ws) {
+        return launch(B, n_steps, G, antithetic, n_outer, n_inner, params, flags, step, coef,
+                      seed, subrun_first, stats, gap_out, cont_out, (double*)ws,
+                      (hipStream_t)stream, div);
+      });
+}
+
+int fdcn_mc_lsm_dual_div_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                               int32_t n_outer, int32_t n_inner, const double* params,
+                               const int32_t* flags, const double* step, const double* div,
+                               const double* coef, uint64_t seed, int64_t subrun_first,
+                               double* stats, double* gap_out, double* cont_out) {
+  int rc = check_sizes(B, n_steps, G, antithetic, n_outer, n_inner, subrun_first);
+  if (rc) return rc;
+  rc = check_pointers("mc_lsm_dual_div_batch", params, flags, step, coef, stats);
+  if (rc) return rc;
+  if (!div) return dfail(FDCN_EINVAL, "mc_lsm_dual_div_batch: div is NULL");
+  rc = check_contracts(B, n_steps, G, params, flags, step, coef);
+  if (rc) return rc;
+  rc = check_dividends(B, n_steps, div);
+  if (rc) return rc;
+  fdcn_internal::HostCall c("mc_lsm_dual_div_batch");
+  if ((rc = c.open())) return rc;
+  const size_t nb = (size_t)B, rows = nb * (size_t)G * (size_t)n_outer;
+  const int rP = c.in(params, sizeof(double) * nb * FDCN_LSM_NPARAM);
+  const int rF = c.in(flags, sizeof(int32_t) * nb * FDCN_LSM_NFLAG);
+  const int rS = c.in(step, sizeof(double) * nb * (size_t)n_steps * FDCN_LSM_NSTEP);
+  const int rD = c.in(div, sizeof(double) * nb * (size_t)n_steps);
+  const int rC = c.in(coef, sizeof(double) * nb * (size_t)G * n_steps * FDCN_LSM_NCOEF);
+  const int rO = c.out(stats, sizeof(double) * nb * FDCN_DUAL_NSTAT);
+  const int rG = c.out(gap_out, sizeof(double) * rows);
+  const int rY = c.out(cont_out, sizeof(double) * rows * (size_t)n_steps);
+  const int rW = c.scratch((size_t)ws_bytes(G) * nb);
+  return c.run([&](hipStream_t stream) {
+    return launch(B, n_steps, G, antithetic, n_outer, n_inner, c.dev<double>(rP),
+                  c.dev<int32_t>(rF), c.dev<double>(rS), c.dev<double>(rC), seed, subrun_first,
+                  c.dev<double>(rO), c.dev<double>(rG), c.dev<double>(rY), c.dev<double>(rW),
+                  stream, c.dev<double>(rD));
   });
 }
 

@@ -43,6 +43,8 @@
 
 #pragma clang fp contract(off)
 
+#include "fdcn_mc_div.h"
+
 namespace {
 
 constexpr int kThreads = 256;
@@ -52,6 +54,8 @@ constexpr int kNSum = 12;                       // moments of one fit
 constexpr int kWsRow = 4;  // per sub-run: sum v, fit-set sum cf, invalid steps, min margin
 static_assert(kSubrun == FDCN_LSM_SUBRUN, "fdcn.h");
 
+using fdcn_div::div_backward;  // the dividend map on the log-spot and its inverse
+using fdcn_div::div_forward;
 using fdcn_philox::normal_pair;
 
 struct LsmArgs {
@@ -71,21 +75,6 @@ __device__ __forceinline__ double payoff(const Contract& c, double s) {
 
 __device__ __forceinline__ bool breach(const Contract& c, double s) {
   return (c.has_lo && s <= c.lower) || (c.has_hi && s >= c.upper);
-}
-
-// The dividend map on the log-spot and its inverse (include/fdcn.h).  g is
-// continuous at 2 D, so a rounding that takes the other branch on the way back
-// moves x by rounding error only.
-constexpr double kLn2 = 0.6931471805599453094;
-
-__device__ __forceinline__ double div_forward(double x, double d) {
-  const double s = exp(x);
-  return s >= 2.0 * d ? log(s - d) : x - kLn2;
-}
-
-__device__ __forceinline__ double div_backward(double x, double d) {
-  const double s = exp(x);
-  return s >= d ? log(s + d) : x + kLn2;
 }
 
 __device__ __forceinline__ double cubic(const double* c, double u) {

@@ -6,7 +6,8 @@
 //
 // The band is compared in x, so exp is evaluated only where something reads
 // the spot: a MONITOR step of a barrier contract, an in-band decision (phi > 0
-// is the last condition of the rule) and maturity.  Include after a
+// is the last condition of the rule), maturity and a step that pays a cash
+// dividend (the map g works on the spot).  Include after a
 // `#pragma clang fp contract(off)`: every operation is rounded separately.
 #pragma once
 
@@ -16,6 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/fdcn.h"
+#include "fdcn_mc_div.h"
 
 namespace fdcn_policy {
 
@@ -57,14 +59,18 @@ __device__ __forceinline__ double band_margin(double x, double lo, double hi) {
 
 // One step of a path under the table rule: step row r, policy row pr
 // (FDCN_POLICY_X_LO, FDCN_POLICY_X_HI).  `stopped` counts the stops of the rule
-// itself, `walked` the steps of paths still alive.
+// itself, `walked` the steps of paths still alive.  dv is the step's cash
+// dividend (uniform; 0.0 for none): paid after the move and before every event,
+// on a step without a flag too, through one exp and one log (fdcn_mc_div.h).
+// Callers without dividends pass the constant 0.0 and the map folds away.
 __device__ __forceinline__ void path_step(const Contract& c, const double* r, const double* pr,
-                                          bool last, double z, double& x, bool& done, bool& in,
-                                          double& val, double& margin, uint64_t& walked,
-                                          uint32_t& stopped) {
+                                          bool last, double z, double dv, double& x, bool& done,
+                                          bool& in, double& val, double& margin,
+                                          uint64_t& walked, uint32_t& stopped) {
   if (done) return;
   ++walked;
   x += r[FDCN_LSM_S_DRIFT] + r[FDCN_LSM_S_DIFF] * z;
+  if (dv != 0.0) x = fdcn_div::div_forward(x, dv);
   const bool mon = c.use_mon && r[FDCN_LSM_S_MONITOR] != 0.0;
   const bool ex = !last && r[FDCN_LSM_S_EXERCISE] != 0.0;
   if (!(mon || ex || last)) return;

@@ -31,6 +31,14 @@
 // floating-point atomics; multiply and add are rounded separately (contraction
 // off), and the sums are the LSM's and the dual's, so a never-stop table
 // reproduces those kernels bit for bit.
+//
+// Both kernels have a second template parameter DIV (the fdcn_mc_policy_div_batch
+// and fdcn_mc_policy_dual_div_batch entries): a step may pay a cash dividend
+// D_m, read from the row div[b][n_steps] with scalar loads like the step rows,
+// so the branch on D_m != 0 is uniform.  Every walk goes forward: after the move
+// the spot goes through g (fdcn_mc_div.h), then the step's events see the
+// ex-dividend spot.  No per-path state is added; DIV = false is the kernel
+// without any of it.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -110,12 +118,13 @@ __device__ __forceinline__ double block_reduce(double* sh, double v, int tid) {
 
 // ---- the lower bound --------------------------------------------------------
 // 107 / 102 VGPRs (antithetic / not), no scratch: 4 waves per SIMD, against the
-// LSM kernel's one.
-template <bool ANTI>
+// LSM kernel's one.  With dividends 111 / 105, still 4 waves.
+template <bool ANTI, bool DIV>
 __global__ void __launch_bounds__(kThreads)
 policy_kernel(PolicyArgs a, const double* __restrict__ params, const int32_t* __restrict__ flags,
               const double* __restrict__ step, const double* __restrict__ policy,
-              double* __restrict__ ws, double* __restrict__ values_out) {
+              double* __restrict__ ws, double* __restrict__ values_out,
+              const double* __restrict__ div) {
   constexpr int kObs = ANTI ? kPerThread / 2 : kPerThread;  // observations per thread
   const int b = blockIdx.x / a.G;  // contract
   const int g = blockIdx.x % a.G;  // sub-run
@@ -125,6 +134,7 @@ policy_kernel(PolicyArgs a, const double* __restrict__ params, const int32_t* __
   const int32_t* F = flags + (size_t)b * FDCN_LSM_NFLAG;
   const double* S = step + (size_t)b * M * FDCN_LSM_NSTEP;
   const double* T = policy + (size_t)b * M * FDCN_POLICY_NCOL;
+  const double* D = DIV ? div + (size_t)b * M : nullptr;  // uniform, like S
   const Contract c = load_contract(P, F);
   const uint32_t w_price = 2u * (uint32_t)F[FDCN_LSM_F_STREAM] + 1u;  // the LSM's price set
   const double x0 = log(P[FDCN_LSM_P_SPOT]);
@@ -150,8 +160,10 @@ policy_kernel(PolicyArgs a, const double* __restrict__ params, const int32_t* __
         const double* ri = S + (size_t)ii * FDCN_LSM_NSTEP;
         const double* ti = T + (size_t)ii * FDCN_POLICY_NCOL;
         const bool last = ii + 1 == M;
-        path_step(c, ri, ti, last, zz[hf], xa, da, ia, va, margin, walked, stopped);
-        if (ANTI) path_step(c, ri, ti, last, -zz[hf], xb, db, ib, vb, margin, walked, stopped);
+        const double dv = DIV ? fdcn_div::div_at(D, ii) : 0.0;
+        path_step(c, ri, ti, last, zz[hf], dv, xa, da, ia, va, margin, walked, stopped);
+        if (ANTI)
+          path_step(c, ri, ti, last, -zz[hf], dv, xb, db, ib, vb, margin, walked, stopped);
       }
       if (da && db) break;
     }
@@ -203,13 +215,15 @@ policy_finalize_kernel(int32_t B, int32_t G, const double* __restrict__ ws,
 // ---- the dual upper bound ---------------------------------------------------
 // fdcn_mc_dual.hip's dual_kernel, statement for statement, with the table rule:
 // 128 / 125 VGPRs (antithetic / not) under the bound of 4 waves per SIMD, no
-// scratch.
-template <bool ANTI>
-__global__ void __launch_bounds__(kThreads, 4)
+// scratch.  The antithetic instance with dividends spills under that bound and
+// is bound to 3 waves instead.
+template <bool ANTI, bool DIV>
+__global__ void __launch_bounds__(kThreads, (ANTI && DIV) ? 3 : 4)
 policy_dual_kernel(DualArgs a, const double* __restrict__ params,
                    const int32_t* __restrict__ flags, const double* __restrict__ step,
                    const double* __restrict__ policy, double* __restrict__ ws,
-                   double* __restrict__ gap_out, double* __restrict__ cont_out) {
+                   double* __restrict__ gap_out, double* __restrict__ cont_out,
+                   const double* __restrict__ div) {
   const int b = blockIdx.x / a.G;  // contract
   const int g = blockIdx.x % a.G;  // sub-run
   const int tid = threadIdx.x;
@@ -218,6 +232,7 @@ policy_dual_kernel(DualArgs a, const double* __restrict__ params,
   const int32_t* F = flags + (size_t)b * FDCN_LSM_NFLAG;
   const double* S = step + (size_t)b * M * FDCN_LSM_NSTEP;
   const double* T = policy + (size_t)b * M * FDCN_POLICY_NCOL;
+  const double* Dv = DIV ? div + (size_t)b * M : nullptr;  // uniform, like S
   const Contract c = load_contract(P, F);
   const uint32_t sid = (uint32_t)F[FDCN_LSM_F_STREAM];
   const uint32_t w_outer = 0x80000000u + 2u * sid, w_inner = w_outer + 1u;
@@ -247,6 +262,10 @@ policy_dual_kernel(DualArgs a, const double* __restrict__ params,
       const double* row = S + (size_t)i * FDCN_LSM_NSTEP;
       const double* tr = T + (size_t)i * FDCN_POLICY_NCOL;
       x += row[FDCN_LSM_S_DRIFT] + row[FDCN_LSM_S_DIFF] * ((i & 1) ? z1 : z0);
+      if (DIV) {  // the dividend, then the step's events on the ex-dividend spot
+        const double dv = fdcn_div::div_at(Dv, i);
+        if (dv != 0.0) x = fdcn_div::div_forward(x, dv);
+      }
       const bool last = i + 1 == M;
       const bool mon = c.use_mon && row[FDCN_LSM_S_MONITOR] != 0.0;
       const bool ex = !last && row[FDCN_LSM_S_EXERCISE] != 0.0;
@@ -282,9 +301,11 @@ policy_dual_kernel(DualArgs a, const double* __restrict__ params,
                 const double* ri = S + (size_t)ii * FDCN_LSM_NSTEP;
                 const double* ti = T + (size_t)ii * FDCN_POLICY_NCOL;
                 const bool li = ii + 1 == M;
-                path_step(c, ri, ti, li, zz[hf], xa, da, ia, va, margin, walked, stopped);
+                const double dv = DIV ? fdcn_div::div_at(Dv, ii) : 0.0;
+                path_step(c, ri, ti, li, zz[hf], dv, xa, da, ia, va, margin, walked, stopped);
                 if (ANTI)
-                  path_step(c, ri, ti, li, -zz[hf], xb, db, ib, vb, margin, walked, stopped);
+                  path_step(c, ri, ti, li, -zz[hf], dv, xb, db, ib, vb, margin, walked,
+                            stopped);
               }
               if (da && db) break;
             }
@@ -456,21 +477,37 @@ int check_contracts(const char* who, int32_t B, int32_t n_steps, const double* p
   return FDCN_OK;
 }
 
+// every dividend finite and >= 0 (a dividend on the last step is legal)
+int check_dividends(const char* who, int32_t B, int32_t n_steps, const double* div) {
+  char msg[160];
+  for (int32_t b = 0; b < B; ++b)
+    for (int32_t m = 0; m < n_steps; ++m) {
+      const double d = div[(size_t)b * n_steps + m];
+      if (isfinite(d) && d >= 0.0) continue;
+      snprintf(msg, sizeof msg, "contract %d: the dividend of step %d %s", b, m + 1,
+               isfinite(d) ? "is negative" : "is not finite");
+      return pfail(who, FDCN_EINVAL, msg);
+    }
+  return FDCN_OK;
+}
+
 int64_t ws_bytes(int32_t G) { return (int64_t)G * kWsRow * (int64_t)sizeof(double); }
 
+// `div` non-null: the DIV instances, an all-zero row included
 int launch_lower(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic, const double* params,
                  const int32_t* flags, const double* step, const double* policy, uint64_t seed,
                  int64_t obs_first, double* stats, double* values_out, double* workspace,
-                 hipStream_t stream) {
+                 hipStream_t stream, const double* div = nullptr) {
   PolicyArgs a;
   a.n_steps = n_steps;
   a.G = G;
   a.obs_first = obs_first;
   a.seed = seed;
   const dim3 grid((uint32_t)((int64_t)B * G)), block(kThreads);
-  auto fn = antithetic ? policy_kernel<true> : policy_kernel<false>;
+  auto fn = div ? (antithetic ? policy_kernel<true, true> : policy_kernel<false, true>)
+                : (antithetic ? policy_kernel<true, false> : policy_kernel<false, false>);
   hipLaunchKernelGGL(fn, grid, block, 0, stream, a, params, flags, step, policy, workspace,
-                     values_out);
+                     values_out, div);
   if (hipGetLastError() != hipSuccess)
     return pfail("mc_policy_batch", FDCN_EHIP, "launch failed");
   hipLaunchKernelGGL(policy_finalize_kernel, dim3((B + kThreads - 1) / kThreads), block, 0,
@@ -483,7 +520,8 @@ int launch_lower(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic, cons
 int launch_dual(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic, int32_t n_outer,
                 int32_t n_inner, const double* params, const int32_t* flags, const double* step,
                 const double* policy, uint64_t seed, int64_t subrun_first, double* stats,
-                double* gap_out, double* cont_out, double* workspace, hipStream_t stream) {
+                double* gap_out, double* cont_out, double* workspace, hipStream_t stream,
+                const double* div = nullptr) {
   DualArgs a;
   a.n_steps = n_steps;
   a.G = G;
@@ -492,9 +530,11 @@ int launch_dual(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic, int32
   a.subrun_first = subrun_first;
   a.seed = seed;
   const dim3 grid((uint32_t)((int64_t)B * G)), block(kThreads);
-  auto fn = antithetic ? policy_dual_kernel<true> : policy_dual_kernel<false>;
+  auto fn = div ? (antithetic ? policy_dual_kernel<true, true> : policy_dual_kernel<false, true>)
+                : (antithetic ? policy_dual_kernel<true, false>
+                              : policy_dual_kernel<false, false>);
   hipLaunchKernelGGL(fn, grid, block, 0, stream, a, params, flags, step, policy, workspace,
-                     gap_out, cont_out);
+                     gap_out, cont_out, div);
   if (hipGetLastError() != hipSuccess)
     return pfail("mc_policy_dual_batch", FDCN_EHIP, "launch failed");
   hipLaunchKernelGGL(policy_dual_finalize_kernel, dim3((B + kThreads - 1) / kThreads), block, 0,
@@ -502,6 +542,111 @@ int launch_dual(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic, int32
   if (hipGetLastError() != hipSuccess)
     return pfail("mc_policy_dual_batch", FDCN_EHIP, "launch failed");
   return FDCN_OK;
+}
+
+
+// The four lower-bound entries: `with_div` is the div form of the contract (div
+// must be there, and a DIV instance runs); div is null otherwise.
+int lower_dev(const char* who, bool with_div, int32_t B, int32_t n_steps, int32_t G,
+              int32_t antithetic, const double* params, const int32_t* flags,
+              const double* step, const double* div, const double* policy, uint64_t seed,
+              int64_t obs_first, double* stats, double* values_out, double* workspace,
+              int64_t workspace_bytes, void* stream) {
+  int rc = check_lower_sizes(who, B, n_steps, G, antithetic, obs_first);
+  if (rc) return rc;
+  rc = check_pointers(who, params, flags, step, policy, stats);
+  if (rc) return rc;
+  if (with_div && !div) return pfail(who, FDCN_EINVAL, "div is NULL");
+  return fdcn_call::with_workspace<fdcn_internal::HipCall>(
+      who, "this launch needs (fdcn_mc_policy_plan)", workspace, workspace_bytes,
+      ws_bytes(G) * B, (hipStream_t)stream, [&](void* ws) {
+        return launch_lower(B, n_steps, G, antithetic, params, flags, step, policy, seed,
+                            obs_first, stats, values_out, (double*)ws, (hipStream_t)stream, div);
+      });
+}
+
+int lower_host(const char* who, bool with_div, int32_t B, int32_t n_steps, int32_t G,
+               int32_t antithetic, const double* params, const int32_t* flags,
+               const double* step, const double* div, const double* policy, uint64_t seed,
+               int64_t obs_first, double* stats, double* values_out) {
+  int rc = check_lower_sizes(who, B, n_steps, G, antithetic, obs_first);
+  if (rc) return rc;
+  rc = check_pointers(who, params, flags, step, policy, stats);
+  if (rc) return rc;
+  if (with_div && !div) return pfail(who, FDCN_EINVAL, "div is NULL");
+  rc = check_contracts(who, B, n_steps, params, flags, step, policy, false);
+  if (rc) return rc;
+  if (with_div && (rc = check_dividends(who, B, n_steps, div))) return rc;
+  fdcn_internal::HostCall c(who);
+  if ((rc = c.open())) return rc;
+  const size_t nb = (size_t)B;
+  const int rP = c.in(params, sizeof(double) * nb * FDCN_LSM_NPARAM);
+  const int rF = c.in(flags, sizeof(int32_t) * nb * FDCN_LSM_NFLAG);
+  const int rS = c.in(step, sizeof(double) * nb * (size_t)n_steps * FDCN_LSM_NSTEP);
+  const int rT = c.in(policy, sizeof(double) * nb * (size_t)n_steps * FDCN_POLICY_NCOL);
+  const int rO = c.out(stats, sizeof(double) * nb * FDCN_POLICY_NSTAT);
+  const int rY = c.out(values_out, sizeof(double) * nb * (size_t)G * kSubrun);
+  const int rW = c.scratch((size_t)ws_bytes(G) * nb);
+  const int rD = c.in(div, sizeof(double) * nb * (size_t)n_steps);  // no room where null
+  return c.run([&](hipStream_t stream) {
+    return launch_lower(B, n_steps, G, antithetic, c.dev<double>(rP), c.dev<int32_t>(rF),
+                        c.dev<double>(rS), c.dev<double>(rT), seed, obs_first,
+                        c.dev<double>(rO), c.dev<double>(rY), c.dev<double>(rW), stream,
+                        c.dev<double>(rD));
+  });
+}
+
+// The four dual entries, in the same way.
+int dual_dev(const char* who, bool with_div, int32_t B, int32_t n_steps, int32_t G,
+             int32_t antithetic, int32_t n_outer, int32_t n_inner, const double* params,
+             const int32_t* flags, const double* step, const double* div, const double* policy,
+             uint64_t seed, int64_t subrun_first, double* stats, double* gap_out,
+             double* cont_out, double* workspace, int64_t workspace_bytes, void* stream) {
+  int rc = check_dual_sizes(who, B, n_steps, G, antithetic, n_outer, n_inner, subrun_first);
+  if (rc) return rc;
+  rc = check_pointers(who, params, flags, step, policy, stats);
+  if (rc) return rc;
+  if (with_div && !div) return pfail(who, FDCN_EINVAL, "div is NULL");
+  return fdcn_call::with_workspace<fdcn_internal::HipCall>(
+      who, "this launch needs (fdcn_mc_policy_dual_plan)", workspace, workspace_bytes,
+      ws_bytes(G) * B, (hipStream_t)stream, [&](void* ws) {
+        return launch_dual(B, n_steps, G, antithetic, n_outer, n_inner, params, flags, step,
+                           policy, seed, subrun_first, stats, gap_out, cont_out, (double*)ws,
+                           (hipStream_t)stream, div);
+      });
+}
+
+int dual_host(const char* who, bool with_div, int32_t B, int32_t n_steps, int32_t G,
+              int32_t antithetic, int32_t n_outer, int32_t n_inner, const double* params,
+              const int32_t* flags, const double* step, const double* div, const double* policy,
+              uint64_t seed, int64_t subrun_first, double* stats, double* gap_out,
+              double* cont_out) {
+  int rc = check_dual_sizes(who, B, n_steps, G, antithetic, n_outer, n_inner, subrun_first);
+  if (rc) return rc;
+  rc = check_pointers(who, params, flags, step, policy, stats);
+  if (rc) return rc;
+  if (with_div && !div) return pfail(who, FDCN_EINVAL, "div is NULL");
+  rc = check_contracts(who, B, n_steps, params, flags, step, policy, true);
+  if (rc) return rc;
+  if (with_div && (rc = check_dividends(who, B, n_steps, div))) return rc;
+  fdcn_internal::HostCall c(who);
+  if ((rc = c.open())) return rc;
+  const size_t nb = (size_t)B, rows = nb * (size_t)G * (size_t)n_outer;
+  const int rP = c.in(params, sizeof(double) * nb * FDCN_LSM_NPARAM);
+  const int rF = c.in(flags, sizeof(int32_t) * nb * FDCN_LSM_NFLAG);
+  const int rS = c.in(step, sizeof(double) * nb * (size_t)n_steps * FDCN_LSM_NSTEP);
+  const int rT = c.in(policy, sizeof(double) * nb * (size_t)n_steps * FDCN_POLICY_NCOL);
+  const int rO = c.out(stats, sizeof(double) * nb * FDCN_DUAL_NSTAT);
+  const int rG = c.out(gap_out, sizeof(double) * rows);
+  const int rY = c.out(cont_out, sizeof(double) * rows * (size_t)n_steps);
+  const int rW = c.scratch((size_t)ws_bytes(G) * nb);
+  const int rD = c.in(div, sizeof(double) * nb * (size_t)n_steps);  // no room where null
+  return c.run([&](hipStream_t stream) {
+    return launch_dual(B, n_steps, G, antithetic, n_outer, n_inner, c.dev<double>(rP),
+                       c.dev<int32_t>(rF), c.dev<double>(rS), c.dev<double>(rT), seed,
+                       subrun_first, c.dev<double>(rO), c.dev<double>(rG), c.dev<double>(rY),
+                       c.dev<double>(rW), stream, c.dev<double>(rD));
+  });
 }
 
 }  // namespace
@@ -523,45 +668,35 @@ int fdcn_mc_policy_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t anti
                              const double* policy, uint64_t seed, int64_t obs_first,
                              double* stats, double* values_out, double* workspace,
                              int64_t workspace_bytes, void* stream) {
-  const char* who = "mc_policy_batch_dev";
-  int rc = check_lower_sizes(who, B, n_steps, G, antithetic, obs_first);
-  if (rc) return rc;
-  rc = check_pointers(who, params, flags, step, policy, stats);
-  if (rc) return rc;
-  return fdcn_call::with_workspace<fdcn_internal::HipCall>(
-      who, "this launch needs (fdcn_mc_policy_plan)", workspace, workspace_bytes,
-      ws_bytes(G) * B, (hipStream_t)stream, [&](void* ws) {
-        return launch_lower(B, n_steps, G, antithetic, params, flags, step, policy, seed,
-                            obs_first, stats, values_out, (double*)ws, (hipStream_t)stream);
-      });
+  return lower_dev("mc_policy_batch_dev", false, B, n_steps, G, antithetic, params, flags, step,
+                   nullptr, policy, seed, obs_first, stats, values_out, workspace,
+                   workspace_bytes, stream);
 }
 
 int fdcn_mc_policy_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
                          const double* params, const int32_t* flags, const double* step,
                          const double* policy, uint64_t seed, int64_t obs_first, double* stats,
                          double* values_out) {
-  const char* who = "mc_policy_batch";
-  int rc = check_lower_sizes(who, B, n_steps, G, antithetic, obs_first);
-  if (rc) return rc;
-  rc = check_pointers(who, params, flags, step, policy, stats);
-  if (rc) return rc;
-  rc = check_contracts(who, B, n_steps, params, flags, step, policy, false);
-  if (rc) return rc;
-  fdcn_internal::HostCall c(who);
-  if ((rc = c.open())) return rc;
-  const size_t nb = (size_t)B;
-  const int rP = c.in(params, sizeof(double) * nb * FDCN_LSM_NPARAM);
-  const int rF = c.in(flags, sizeof(int32_t) * nb * FDCN_LSM_NFLAG);
-  const int rS = c.in(step, sizeof(double) * nb * (size_t)n_steps * FDCN_LSM_NSTEP);
-  const int rT = c.in(policy, sizeof(double) * nb * (size_t)n_steps * FDCN_POLICY_NCOL);
-  const int rO = c.out(stats, sizeof(double) * nb * FDCN_POLICY_NSTAT);
-  const int rY = c.out(values_out, sizeof(double) * nb * (size_t)G * kSubrun);
-  const int rW = c.scratch((size_t)ws_bytes(G) * nb);
-  return c.run([&](hipStream_t stream) {
-    return launch_lower(B, n_steps, G, antithetic, c.dev<double>(rP), c.dev<int32_t>(rF),
-                        c.dev<double>(rS), c.dev<double>(rT), seed, obs_first,
-                        c.dev<double>(rO), c.dev<double>(rY), c.dev<double>(rW), stream);
-  });
+  return lower_host("mc_policy_batch", false, B, n_steps, G, antithetic, params, flags, step,
+                    nullptr, policy, seed, obs_first, stats, values_out);
+}
+
+int fdcn_mc_policy_div_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                                 const double* params, const int32_t* flags, const double* step,
+                                 const double* div, const double* policy, uint64_t seed,
+                                 int64_t obs_first, double* stats, double* values_out,
+                                 double* workspace, int64_t workspace_bytes, void* stream) {
+  return lower_dev("mc_policy_div_batch_dev", true, B, n_steps, G, antithetic, params, flags,
+                   step, div, policy, seed, obs_first, stats, values_out, workspace,
+                   workspace_bytes, stream);
+}
+
+int fdcn_mc_policy_div_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                             const double* params, const int32_t* flags, const double* step,
+                             const double* div, const double* policy, uint64_t seed,
+                             int64_t obs_first, double* stats, double* values_out) {
+  return lower_host("mc_policy_div_batch", true, B, n_steps, G, antithetic, params, flags, step,
+                    div, policy, seed, obs_first, stats, values_out);
 }
 
 int fdcn_mc_policy_dual_plan(int32_t n_steps, int32_t G, int32_t antithetic, int32_t n_outer,
@@ -582,18 +717,9 @@ int fdcn_mc_policy_dual_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t
                                   const double* policy, uint64_t seed, int64_t subrun_first,
                                   double* stats, double* gap_out, double* cont_out,
                                   double* workspace, int64_t workspace_bytes, void* stream) {
-  const char* who = "mc_policy_dual_batch_dev";
-  int rc = check_dual_sizes(who, B, n_steps, G, antithetic, n_outer, n_inner, subrun_first);
-  if (rc) return rc;
-  rc = check_pointers(who, params, flags, step, policy, stats);
-  if (rc) return rc;
-  return fdcn_call::with_workspace<fdcn_internal::HipCall>(
-      who, "this launch needs (fdcn_mc_policy_dual_plan)", workspace, workspace_bytes,
-      ws_bytes(G) * B, (hipStream_t)stream, [&](void* ws) {
-        return launch_dual(B, n_steps, G, antithetic, n_outer, n_inner, params, flags, step,
-                           policy, seed, subrun_first, stats, gap_out, cont_out, (double*)ws,
-                           (hipStream_t)stream);
-      });
+  return dual_dev("mc_policy_dual_batch_dev", false, B, n_steps, G, antithetic, n_outer, n_inner,
+                  params, flags, step, nullptr, policy, seed, subrun_first, stats, gap_out,
+                  cont_out, workspace, workspace_bytes, stream);
 }
 
 int fdcn_mc_policy_dual_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
@@ -601,30 +727,31 @@ int fdcn_mc_policy_dual_batch(int32_t B, int32_t n_steps, int32_t G, int32_t ant
                               const int32_t* flags, const double* step, const double* policy,
                               uint64_t seed, int64_t subrun_first, double* stats,
                               double* gap_out, double* cont_out) {
-  const char* who = "mc_policy_dual_batch";
-  int rc = check_dual_sizes(who, B, n_steps, G, antithetic, n_outer, n_inner, subrun_first);
-  if (rc) return rc;
-  rc = check_pointers(who, params, flags, step, policy, stats);
-  if (rc) return rc;
-  rc = check_contracts(who, B, n_steps, params, flags, step, policy, true);
-  if (rc) return rc;
-  fdcn_internal::HostCall c(who);
-  if ((rc = c.open())) return rc;
-  const size_t nb = (size_t)B, rows = nb * (size_t)G * (size_t)n_outer;
-  const int rP = c.in(params, sizeof(double) * nb * FDCN_LSM_NPARAM);
-  const int rF = c.in(flags, sizeof(int32_t) * nb * FDCN_LSM_NFLAG);
-  const int rS = c.in(step, sizeof(double) * nb * (size_t)n_steps * FDCN_LSM_NSTEP);
-  const int rT = c.in(policy, sizeof(double) * nb * (size_t)n_steps * FDCN_POLICY_NCOL);
-  const int rO = c.out(stats, sizeof(double) * nb * FDCN_DUAL_NSTAT);
-  const int rG = c.out(gap_out, sizeof(double) * rows);
-  const int rY = c.out(cont_out, sizeof(double) * rows * (size_t)n_steps);
-  const int rW = c.scratch((size_t)ws_bytes(G) * nb);
-  return c.run([&](hipStream_t stream) {
-    return launch_dual(B, n_steps, G, antithetic, n_outer, n_inner, c.dev<double>(rP),
-                       c.dev<int32_t>(rF), c.dev<double>(rS), c.dev<double>(rT), seed,
-                       subrun_first, c.dev<double>(rO), c.dev<double>(rG), c.dev<double>(rY),
-                       c.dev<double>(rW), stream);
-  });
+  return dual_host("mc_policy_dual_batch", false, B, n_steps, G, antithetic, n_outer, n_inner,
+                   params, flags, step, nullptr, policy, seed, subrun_first, stats, gap_out,
+                   cont_out);
+}
+
+int fdcn_mc_policy_dual_div_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                                      int32_t n_outer, int32_t n_inner, const double* params,
+                                      const int32_t* flags, const double* step,
+                                      const double* div, const double* policy, uint64_t seed,
+                                      int64_t subrun_first, double* stats, double* gap_out,
+                                      double* cont_out, double* workspace,
+                                      int64_t workspace_bytes, void* stream) {
+  return dual_dev("mc_policy_dual_div_batch_dev", true, B, n_steps, G, antithetic, n_outer,
+                  n_inner, params, flags, step, div, policy, seed, subrun_first, stats, gap_out,
+                  cont_out, workspace, workspace_bytes, stream);
+}
+
+int fdcn_mc_policy_dual_div_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                                  int32_t n_outer, int32_t n_inner, const double* params,
+                                  const int32_t* flags, const double* step, const double* div,
+                                  const double* policy, uint64_t seed, int64_t subrun_first,
+                                  double* stats, double* gap_out, double* cont_out) {
+  return dual_host("mc_policy_dual_div_batch", true, B, n_steps, G, antithetic, n_outer,
+                   n_inner, params, flags, step, div, policy, seed, subrun_first, stats, gap_out,
+                   cont_out);
 }
 
 }  // extern "C"

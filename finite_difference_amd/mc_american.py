@@ -41,7 +41,10 @@ there -- which gives a gap >= 0 such that price + gap is an upper bound in
 expectation whatever the policy (include/fdcn.h, fdcn_mc_lsm_dual_batch;
 csrc/fdcn_mc_dual.hip on the device, ``host_dual_subruns`` in NumPy).
 ``brackets`` is the comparison of an FD price with the two bounds.  Cash
-dividends are out of scope there: a contract that carries them is refused.
+dividends are opt-in there too (``cash_dividends="path"``): both walks of the
+dual pay a step's dividend after its move and before its events
+(fdcn_mc_lsm_dual_div_batch); by default a contract that carries them is
+refused.
 
 Both bounds also run under a *given* exercise rule instead of the fitted one
 (``mc_policy_batch``, ``mc_policy_bounds_batch``): an ``ExercisePolicy`` is a
@@ -50,7 +53,10 @@ exercise boundary a BermudanFDMPricer has computed.  Any rule gives a lower
 bound and any rule gives a dual upper bound, so the FD boundary can drive
 both without circularity: a wrong boundary shows as a low lower bound and a
 wide gap, not as agreement (include/fdcn.h, fdcn_mc_policy_batch;
-csrc/fdcn_mc_policy.hip; ``host_policy_subruns`` in NumPy).
+csrc/fdcn_mc_policy.hip; ``host_policy_subruns`` in NumPy).  With
+``cash_dividends="path"`` the table bounds take dividend contracts as well, and
+``policy_from_pricer`` a Bermudan pricer with dividends in its life (DESIGN
+section 13.5).
 
 A missing GPU under ``engine="hip"`` is an error, never a silent fallback.
 """
@@ -805,8 +811,8 @@ def _check_dual_sizes(n_outer, n_inner, antithetic: bool) -> None:
                          f"antithetic) up to {capi.DUAL_MAX_INNER}")
 
 
-def _check_dual_contract(c: LsmContract) -> None:
-    if c.has_dividends:
+def _check_dual_contract(c: LsmContract, cash_dividends: str = "refuse") -> None:
+    if c.has_dividends and _check_cash_dividends(cash_dividends) == "refuse":
         raise ValueError("cash dividends are out of the dual bound's scope.")
     if int(c.flags[capi.LSM_F_KIND]) != 0 and np.any(c.step[:, capi.LSM_S_REBATE] < 0.0):
         raise ValueError("a negative rebate: the dual bound needs every cashflow >= 0.")
@@ -853,25 +859,31 @@ class _TableRule:
 
 
 def host_dual_subruns(c: LsmContract, coef: np.ndarray, subruns: Sequence[int], n_outer: int,
-                      n_inner: int, antithetic: bool, seed: int, stream_id: int) -> dict:
+                      n_inner: int, antithetic: bool, seed: int, stream_id: int,
+                      cash_dividends: str = "refuse") -> dict:
     """The dual estimator for the sub-runs `subruns` (absolute numbers) of
     contract c under the policies coef [g, n_steps, LSM_NCOEF], row for row of
     `subruns`: the kernel's operations per path on the same streams, the g *
     n_outer outer paths side by side.  -> gaps [g, n_outer] (D per outer
     path), cont [g, n_outer, n_steps] (the inner means, 0.0 where none was
-    run), margin [g], inner_paths [g], inner_steps [g]."""
+    run), margin [g], inner_paths [g], inner_steps [g].  A contract that
+    carries dividends needs cash_dividends="path": each step's dividend then
+    follows its move on the outer and the inner walks (include/fdcn.h,
+    fdcn_mc_lsm_dual_div_batch)."""
     coef = np.asarray(coef, dtype=float)
     if coef.shape != (len(subruns), c.n_steps, capi.LSM_NCOEF):
         raise ValueError("host_dual_subruns: coef [len(subruns), n_steps, LSM_NCOEF]")
     rule = _FittedRule(c, coef, np.repeat(np.arange(len(subruns)), int(n_outer)))
-    return _host_dual(c, rule, subruns, n_outer, n_inner, antithetic, seed, stream_id)
+    return _host_dual(c, rule, subruns, n_outer, n_inner, antithetic, seed, stream_id,
+                      cash_dividends)
 
 
 def _host_dual(c: LsmContract, rule, subruns: Sequence[int], n_outer: int, n_inner: int,
-               antithetic: bool, seed: int, stream_id: int) -> dict:
+               antithetic: bool, seed: int, stream_id: int,
+               cash_dividends: str = "refuse") -> dict:
     """host_dual_subruns under `rule` (_FittedRule or _TableRule)."""
     _check_dual_sizes(n_outer, n_inner, bool(antithetic))
-    _check_dual_contract(c)
+    _check_dual_contract(c, cash_dividends)
     P, F, S = c.params, c.flags, c.step
     M, ng = c.n_steps, len(subruns)
     if any(not 0 <= int(g) < 2 ** 31 for g in subruns):
@@ -909,6 +921,7 @@ def _host_dual(c: LsmContract, rule, subruns: Sequence[int], n_outer: int, n_inn
     exr = S[:, capi.LSM_S_EXERCISE] != 0.0
     exr[M - 1] = False
     reb, dfe = S[:, capi.LSM_S_REBATE], S[:, capi.LSM_S_DF_END]
+    Dv = c.div_row()  # after the move, before the step's events, on both walks
 
     R = ng * n_outer                                   # outer paths, row = g * n_outer + p
     sub = np.repeat(np.asarray([int(g) for g in subruns], dtype=np.uint64), n_outer)
@@ -938,6 +951,8 @@ def _host_dual(c: LsmContract, rule, subruns: Sequence[int], n_outer: int, n_inn
             ii = i + 1 + t
             walked[rows] += np.sum(~done, axis=1)
             x = x + (drift[ii] + diff[ii] * (z[:, obs_of, t] * sign[None, :]))
+            if Dv[ii] != 0.0:
+                x = _div_forward(x, Dv[ii])
             ruled = bool(exr[ii]) and rule.any_at(rows, ii)
             if not (mon[ii] or ii == M - 1 or ruled):
                 continue
@@ -968,6 +983,8 @@ def _host_dual(c: LsmContract, rule, subruns: Sequence[int], n_outer: int, n_inn
     alive = np.ones(R, dtype=bool)
     for i in range(M):
         x = x + (drift[i] + diff[i] * Zo[:, i])
+        if Dv[i] != 0.0:
+            x = _div_forward(x, Dv[i])
         last = i == M - 1
         if not (mon[i] or exr[i] or last):
             continue
@@ -1040,12 +1057,16 @@ def merge_dual_stats(parts) -> Dict[str, float]:
 def simulate_dual(group: Sequence[LsmContract], coef: np.ndarray, n_outer: int, n_inner: int,
                   antithetic: bool, *, engine: str = "hip", seed: int = 0,
                   stream_ids: Optional[Sequence[int]] = None, subrun_first: int = 0,
-                  want_gap: bool = False, want_cont: bool = False, host_chunk: int = 16) -> dict:
+                  want_gap: bool = False, want_cont: bool = False, host_chunk: int = 16,
+                  cash_dividends: str = "refuse") -> dict:
     """The dual estimator for contracts that share n_steps, under the policies
     coef [B, G, n_steps, LSM_NCOEF] -- simulate_lsm's "coef" of sub-runs
     subrun_first .. subrun_first + G - 1 with the same seed and stream ids.
     -> {"stats": [B, DUAL_NSTAT]} plus "gap" [B, G * n_outer] and "cont"
-    [B, G * n_outer, n_steps] where asked for."""
+    [B, G * n_outer, n_steps] where asked for.  Contracts that carry dividends
+    need cash_dividends="path"; one of them sends the launch through the div
+    entry."""
+    _check_cash_dividends(cash_dividends)
     if engine not in ("hip", "host"):
         raise ValueError("engine must be 'hip' or 'host'")
     B = len(group)
@@ -1078,13 +1099,13 @@ def simulate_dual(group: Sequence[LsmContract], coef: np.ndarray, n_outer: int, 
     if any(not 0 <= s < 2 ** 30 for s in ids):
         raise ValueError("simulate_dual: stream ids must be in 0 .. 2^30 - 1")
     for c in group:
-        _check_dual_contract(c)
+        _check_dual_contract(c, cash_dividends)
     if engine == "hip":
         capi.require_device()
         P, F, S = _stack(group, ids)
         stats, gap, cont = capi.mc_dual_batch(P, F, S, coef, n_outer, n_inner, antithetic,
                                               seed=seed, subrun_first=first, want_gap=want_gap,
-                                              want_cont=want_cont)
+                                              want_cont=want_cont, div=_div_rows(group))
     else:
         stats = np.empty((B, capi.DUAL_NSTAT))
         gap = np.empty((B, G * n_outer))
@@ -1095,7 +1116,7 @@ def simulate_dual(group: Sequence[LsmContract], coef: np.ndarray, n_outer: int, 
             for lo in range(0, G, step):
                 hi = min(G, lo + step)
                 r = host_dual_subruns(c, coef[b, lo:hi], range(first + lo, first + hi), n_outer,
-                                      n_inner, antithetic, seed, ids[b])
+                                      n_inner, antithetic, seed, ids[b], cash_dividends)
                 gap[b, lo * n_outer:hi * n_outer] = r["gaps"].reshape(-1)
                 if want_cont:
                     cont[b, lo * n_outer:hi * n_outer] = r["cont"].reshape(-1, n_steps)
@@ -1136,11 +1157,14 @@ def _bounds_result(res: dict, dual: DualConfig, st: Optional[np.ndarray]) -> dic
 def mc_american_bounds_batch(contracts: Sequence, cfg: LsmConfig = LsmConfig(),
                              dual: DualConfig = DualConfig(), *, engine: str = "hip",
                              stream_ids: Optional[Sequence[int]] = None,
-                             subrun_range: Optional[range] = None) -> List[dict]:
-    """Lower and upper bound of many contracts: per distinct step count one
-    least-squares Monte Carlo launch that keeps its coefficients, then one
-    dual launch under them.  Arguments as mc_american_batch (contracts with
-    cash dividends are refused).  Results, in input order: mc_american_batch's
+                             subrun_range: Optional[range] = None,
+                             cash_dividends: str = "refuse") -> List[dict]:
+    """Lower and upper bound of many contracts: per distinct (step count, has
+    dividends) one least-squares Monte Carlo launch that keeps its
+    coefficients, then one dual launch under them.  Arguments as
+    mc_american_batch; contracts with cash dividends are refused unless
+    cash_dividends="path", which also plans the keyword contracts that do not
+    name a mode of their own.  Results, in input order: mc_american_batch's
     dict plus "gap" and "gap_stderr" (mean and standard error of the sub-run
     gaps), "upper" = price + gap, "upper_stderr" = sqrt(stderr^2 +
     gap_stderr^2), "n_outer", "n_inner", "sum_gap" and "sum_gap2"
@@ -1152,9 +1176,15 @@ def mc_american_bounds_batch(contracts: Sequence, cfg: LsmConfig = LsmConfig(),
     biases the gap upward by an amount that shrinks with n_inner: the safe
     side for an upper bound.  A contract with a `fixed_price` gets gap 0 and
     upper = price."""
-    plans = [c if isinstance(c, LsmContract) else plan_american_contract(**c) for c in contracts]
+    if _check_cash_dividends(cash_dividends) == "refuse":
+        plans = [c if isinstance(c, LsmContract) else plan_american_contract(**c)
+                 for c in contracts]
+    else:
+        plans = [c if isinstance(c, LsmContract)
+                 else plan_american_contract(**{"cash_dividends": cash_dividends, **c})
+                 for c in contracts]
     for c in plans:
-        _check_dual_contract(c)
+        _check_dual_contract(c, cash_dividends)
     _check_dual_sizes(dual.n_outer, dual.n_inner, bool(cfg.antithetic))
     lo, hi = 0, int(cfg.n_subruns)
     if hi < 1:
@@ -1168,18 +1198,19 @@ def mc_american_bounds_batch(contracts: Sequence, cfg: LsmConfig = LsmConfig(),
     if len(ids) != len(plans):
         raise ValueError("one stream id per contract")
     out: List[Optional[dict]] = [None] * len(plans)
-    by_steps: Dict[int, List[int]] = {}
+    by_steps: Dict[tuple, List[int]] = {}
     for k, c in enumerate(plans):
         if c.fixed_price is not None:
             out[k] = _bounds_result(_result(c, cfg, hi - lo, None), dual, None)
         else:
-            by_steps.setdefault(c.n_steps, []).append(k)
+            by_steps.setdefault((c.n_steps, c.has_dividends), []).append(k)
     for members in by_steps.values():
         group = [plans[k] for k in members]
         kw = dict(engine=engine, seed=cfg.seed, stream_ids=[ids[k] for k in members],
                   subrun_first=lo)
         r = simulate_lsm(group, hi - lo, cfg.antithetic, want_coef=True, **kw)
-        d = simulate_dual(group, r["coef"], dual.n_outer, dual.n_inner, cfg.antithetic, **kw)
+        d = simulate_dual(group, r["coef"], dual.n_outer, dual.n_inner, cfg.antithetic,
+                          cash_dividends=cash_dividends, **kw)
         for row, k in enumerate(members):
             out[k] = _bounds_result(_result(plans[k], cfg, hi - lo, r["stats"][row]), dual,
                                     d["stats"][row])
@@ -1189,17 +1220,20 @@ def mc_american_bounds_batch(contracts: Sequence, cfg: LsmConfig = LsmConfig(),
 def price_american_mc_bounds(contract: Optional[LsmContract] = None, *, n_subruns: int = 32,
                              antithetic: bool = True, seed: int = 42, stream_id: int = 0,
                              n_outer: int = 8, n_inner: int = 2048, engine: str = "hip",
-                             **plan_kw) -> Dict[str, object]:
+                             cash_dividends: str = "refuse", **plan_kw) -> Dict[str, object]:
     """Lower and upper bound of one contract -- an LsmContract, or the keyword
-    arguments of plan_american_contract: price_american_mc's keys plus those
-    mc_american_bounds_batch adds."""
+    arguments of plan_american_contract (`dividends` needs
+    cash_dividends="path", which plans and permits with the one keyword):
+    price_american_mc's keys plus those mc_american_bounds_batch adds."""
+    _check_cash_dividends(cash_dividends)
     if contract is None:
-        contract = plan_american_contract(**plan_kw)
+        contract = plan_american_contract(cash_dividends=cash_dividends, **plan_kw)
     elif plan_kw:
         raise TypeError("give a contract or the keywords of plan_american_contract, not both")
     cfg = LsmConfig(n_subruns=int(n_subruns), antithetic=bool(antithetic), seed=int(seed))
     return mc_american_bounds_batch([contract], cfg, DualConfig(int(n_outer), int(n_inner)),
-                                    engine=engine, stream_ids=[stream_id])[0]
+                                    engine=engine, stream_ids=[stream_id],
+                                    cash_dividends=cash_dividends)[0]
 
 
 def brackets(result: dict, fd_price: float, grid_error: float = 0.0, z: float = 5.0) -> bool:
@@ -1259,18 +1293,41 @@ class ExercisePolicy:
         log-spot of the pair (X_LO = -inf), a call at and above it (X_HI =
         +inf); s_below = 0 or s_above = inf puts the threshold at that end.
         Every EXERCISE step before maturity needs an entry, and every entry a
-        step; the other steps get "never"."""
+        step; the other steps get "never".
+
+        A contract of the American kind planned with cash dividends has two
+        steps at a dividend date t_d (plan_american_contract): the exercise on
+        the cum-dividend spot, then the zero-length step that pays the dividend
+        and exercises on the ex-dividend spot.  Such a time takes
+        {"cum": pair_or_None, "ex": pair_or_None}, one entry per step; a plain
+        pair there is an error, because it would not say which spot it is in."""
         M = contract.n_steps
         put = bool(contract.flags[capi.LSM_F_PUT])
         pol = cls.never(M)
         ex = contract.step[:, capi.LSM_S_EXERCISE] != 0.0
         ex[M - 1] = False
         seen = np.zeros(M, dtype=bool)
+        entries: List[tuple] = []  # (step, pair or None)
         for t, pair in spots.items():
             i = int(np.argmin(np.abs(contract.times - float(t))))
             if abs(float(contract.times[i]) - float(t)) > _MERGE or seen[i]:
                 raise ValueError(f"from_critical_spots: time {t!r} is not one step of the contract")
-            seen[i] = True
+            two = i + 1 < M and abs(float(contract.times[i + 1] - contract.times[i])) <= _MERGE
+            if two:
+                if not (isinstance(pair, dict) and set(pair) == {"cum", "ex"}):
+                    raise ValueError(
+                        f"from_critical_spots: time {t!r} is a dividend date of two steps "
+                        f"({i + 1}: cum-dividend, {i + 2}: ex-dividend): give "
+                        "{'cum': pair_or_None, 'ex': pair_or_None}")
+                seen[i] = seen[i + 1] = True
+                entries += [(i, pair["cum"]), (i + 1, pair["ex"])]
+            else:
+                if isinstance(pair, dict):
+                    raise ValueError(f"from_critical_spots: time {t!r} is one step, not a "
+                                     "cum- / ex-dividend pair of steps")
+                seen[i] = True
+                entries.append((i, pair))
+        for i, pair in entries:
             if pair is None:
                 continue
             below, above = float(pair[0]), float(pair[1])
@@ -1292,9 +1349,10 @@ class ExercisePolicy:
 
 
 def policy_from_pricer(p, contract: Optional[LsmContract] = None,
-                       n_time: Optional[int] = None) -> ExercisePolicy:
+                       n_time: Optional[int] = None,
+                       cash_dividends: str = "refuse") -> ExercisePolicy:
     """The exercise boundary of the BermudanFDMPricer `p` as the policy of
-    `contract` (default: contract_from_pricer(p)).
+    `contract` (default: contract_from_pricer(p, cash_dividends=cash_dividends)).
 
     `p.exercise_boundary(n_time)` gives, per exercise date, the nodes at which
     the payoff exceeded the continuation value; its records are matched to
@@ -1312,18 +1370,26 @@ def policy_from_pricer(p, contract: Optional[LsmContract] = None,
     simulated on the grid k T / n_exercise, which no boundary record lies on.
     A knock-in contract takes the policy of a vanilla Bermudan twin: give the
     twin as `p` and the knock-in contract (same exercise times) as `contract`;
-    the Monte Carlo applies the rule from the hit step on.  Pricers with cash
-    dividends are refused: they are out of the table policy's scope."""
+    the Monte Carlo applies the rule from the hit step on.
+
+    Pricers and contracts with cash dividends in their life are refused unless
+    cash_dividends="path".  The Bermudan class takes a date's dividend first
+    and then the date's events on the ex-dividend spot (marching backward: the
+    exercise event, then the dividend jump), and so does the contract's single
+    step of that date.  The boundary record of an exercise date that is also a
+    dividend date is therefore already in ex-dividend spots and maps to its
+    step unchanged."""
     from .bermudan import BermudanFDMPricer
     if not isinstance(p, BermudanFDMPricer):
         raise ValueError(f"policy_from_pricer takes a BermudanFDMPricer, not {type(p).__name__}: "
                          "only Bermudan exercise dates coincide with the contract's steps (the "
                          "American classes are simulated on the grid k T / n_exercise).")
-    if p._div_times_tau():
+    refuse = _check_cash_dividends(cash_dividends) == "refuse"
+    if refuse and p._div_times_tau():
         raise ValueError("cash dividends are out of the table policy's scope.")
     if contract is None:
-        contract = contract_from_pricer(p)
-    if contract.has_dividends:
+        contract = contract_from_pricer(p, cash_dividends=cash_dividends)
+    if refuse and contract.has_dividends:
         raise ValueError("cash dividends are out of the table policy's scope.")
     put = p.option_type == "put"
     if put != bool(contract.flags[capi.LSM_F_PUT]):
@@ -1342,23 +1408,35 @@ def policy_from_pricer(p, contract: Optional[LsmContract] = None,
     return ExercisePolicy.from_critical_spots(contract, spots)
 
 
-def _check_policy(c: LsmContract, policy: ExercisePolicy) -> None:
+def _check_policy(c: LsmContract, policy: ExercisePolicy,
+                  cash_dividends: str = "refuse") -> None:
     if not isinstance(policy, ExercisePolicy):
         raise TypeError("an ExercisePolicy per contract")
     if policy.n_steps != c.n_steps:
         raise ValueError(f"the policy has {policy.n_steps} steps, the contract {c.n_steps}")
-    if c.has_dividends:
+    if c.has_dividends and _check_cash_dividends(cash_dividends) == "refuse":
         raise ValueError("cash dividends are out of the table policy's scope.")
 
 
+def _div_rows(group: Sequence[LsmContract]) -> Optional[np.ndarray]:
+    """div [B, n_steps] of a launch: one contract with a dividend sends the
+    launch through the div entry; None takes the plain one."""
+    if not any(c.has_dividends for c in group):
+        return None
+    return np.stack([c.div_row() for c in group])
+
+
 def host_policy_subruns(c: LsmContract, policy: ExercisePolicy, subruns: Sequence[int],
-                        antithetic: bool, seed: int, stream_id: int) -> dict:
+                        antithetic: bool, seed: int, stream_id: int,
+                        cash_dividends: str = "refuse") -> dict:
     """The sub-runs `subruns` of contract c under `policy` on the host: the
     kernel's operations per path on the LSM's price-set streams.  -> values
     [g, LSM_SUBRUN], stop_step [g, LSM_SUBRUN] (the step m at which each path
     stopped), means [g] (the kernel's sum: slot order, then the fixed tree),
-    margin [g], exercised [g] (paths the rule stopped)."""
-    _check_policy(c, policy)
+    margin [g], exercised [g] (paths the rule stopped).  A contract that
+    carries dividends needs cash_dividends="path": each step's dividend then
+    follows its move and precedes its events (fdcn_mc_policy_div_batch)."""
+    _check_policy(c, policy, cash_dividends)
     P, F, S = c.params, c.flags, c.step
     M, ng, n = c.n_steps, len(subruns), capi.LSM_SUBRUN
     strike, lower, upper = float(P[capi.LSM_P_STRIKE]), float(P[capi.LSM_P_LOWER]), \
@@ -1385,6 +1463,7 @@ def host_policy_subruns(c: LsmContract, policy: ExercisePolicy, subruns: Sequenc
     exr = S[:, capi.LSM_S_EXERCISE] != 0.0
     exr[M - 1] = False
     reb, dfe = S[:, capi.LSM_S_REBATE], S[:, capi.LSM_S_DF_END]
+    Dv = c.div_row()
     rule = _TableRule(policy)
     Z = np.stack([_path_normals(M, seed, 2 * int(stream_id) + 1, int(g) * per, antithetic)
                   for g in subruns])
@@ -1398,6 +1477,8 @@ def host_policy_subruns(c: LsmContract, policy: ExercisePolicy, subruns: Sequenc
     for m in range(1, M + 1):
         i = m - 1
         x = x + (drift[i] + diff[i] * Z[:, :, i])
+        if Dv[i] != 0.0:
+            x = _div_forward(x, Dv[i])
         if not (mon[i] or exr[i] or m == M):
             continue
         s = np.exp(x)
@@ -1428,12 +1509,12 @@ def host_policy_subruns(c: LsmContract, policy: ExercisePolicy, subruns: Sequenc
 
 def host_policy_dual_subruns(c: LsmContract, policy: ExercisePolicy, subruns: Sequence[int],
                              n_outer: int, n_inner: int, antithetic: bool, seed: int,
-                             stream_id: int) -> dict:
+                             stream_id: int, cash_dividends: str = "refuse") -> dict:
     """host_dual_subruns under the table `policy` (one for all sub-runs) in the
     place of the fitted coefficients: the same streams, sums and outputs."""
-    _check_policy(c, policy)
+    _check_policy(c, policy, cash_dividends)
     return _host_dual(c, _TableRule(policy), subruns, n_outer, n_inner, antithetic, seed,
-                      stream_id)
+                      stream_id, cash_dividends)
 
 
 def _finalize_policy(means: np.ndarray, margin: float, exercised: float) -> np.ndarray:
@@ -1461,7 +1542,9 @@ def merge_policy_stats(parts) -> Dict[str, float]:
     return out
 
 
-def _policy_group(who: str, group, policies, n_subruns, subrun_first, stream_ids, engine):
+def _policy_group(who: str, group, policies, n_subruns, subrun_first, stream_ids, engine,
+                  cash_dividends: str = "refuse"):
+    _check_cash_dividends(cash_dividends)
     if engine not in ("hip", "host"):
         raise ValueError("engine must be 'hip' or 'host'")
     B = len(group)
@@ -1475,7 +1558,7 @@ def _policy_group(who: str, group, policies, n_subruns, subrun_first, stream_ids
     if n_steps > capi.LSM_MAX_STEPS:
         raise ValueError(f"{who}: at most {capi.LSM_MAX_STEPS} steps")
     for c, pol in zip(group, policies):
-        _check_policy(c, pol)
+        _check_policy(c, pol, cash_dividends)
     G = int(n_subruns)
     if G < 1:
         raise ValueError(f"{who}: n_subruns must be >= 1")
@@ -1494,12 +1577,15 @@ def _policy_group(who: str, group, policies, n_subruns, subrun_first, stream_ids
 def simulate_policy(group: Sequence[LsmContract], policies: Sequence[ExercisePolicy],
                     n_subruns: int, antithetic: bool, *, engine: str = "hip", seed: int = 0,
                     stream_ids: Optional[Sequence[int]] = None, subrun_first: int = 0,
-                    want_values: bool = False, host_chunk: int = 16) -> dict:
+                    want_values: bool = False, host_chunk: int = 16,
+                    cash_dividends: str = "refuse") -> dict:
     """simulate_lsm under given policies, one per contract: -> {"stats":
     [B, POLICY_NSTAT]} plus "values" [B, n_subruns * LSM_SUBRUN] where asked
-    for, the paths those of simulate_lsm's "values"."""
+    for, the paths those of simulate_lsm's "values".  Contracts that carry
+    dividends need cash_dividends="path"; one of them sends the launch through
+    the div entry."""
     B, n_steps, G, first, ids = _policy_group("simulate_policy", group, policies, n_subruns,
-                                              subrun_first, stream_ids, engine)
+                                              subrun_first, stream_ids, engine, cash_dividends)
     antithetic = bool(antithetic)
     if engine == "hip":
         capi.require_device()
@@ -1507,7 +1593,7 @@ def simulate_policy(group: Sequence[LsmContract], policies: Sequence[ExercisePol
         T = np.stack([pol.table() for pol in policies])
         stats, val = capi.mc_policy_batch(P, F, S, T, G, antithetic, seed=seed,
                                           obs_first=first * obs_per_subrun(antithetic),
-                                          want_values=want_values)
+                                          want_values=want_values, div=_div_rows(group))
     else:
         stats = np.empty((B, capi.POLICY_NSTAT))
         val = np.empty((B, G * capi.LSM_SUBRUN)) if want_values else None
@@ -1518,7 +1604,7 @@ def simulate_policy(group: Sequence[LsmContract], policies: Sequence[ExercisePol
             for lo in range(0, G, step):
                 hi = min(G, lo + step)
                 r = host_policy_subruns(c, pol, range(first + lo, first + hi), antithetic, seed,
-                                        ids[b])
+                                        ids[b], cash_dividends)
                 means[lo:hi] = r["means"]
                 margin = min(margin, float(r["margin"].min()))
                 exercised += float(r["exercised"].sum())
@@ -1536,24 +1622,25 @@ def simulate_policy_dual(group: Sequence[LsmContract], policies: Sequence[Exerci
                          engine: str = "hip", seed: int = 0,
                          stream_ids: Optional[Sequence[int]] = None, subrun_first: int = 0,
                          want_gap: bool = False, want_cont: bool = False,
-                         host_chunk: int = 16) -> dict:
+                         host_chunk: int = 16, cash_dividends: str = "refuse") -> dict:
     """simulate_dual under given policies, one per contract: -> {"stats":
     [B, DUAL_NSTAT]} plus "gap" [B, G * n_outer] and "cont" [B, G * n_outer,
-    n_steps] where asked for."""
+    n_steps] where asked for; cash_dividends as in simulate_policy."""
     B, n_steps, G, first, ids = _policy_group("simulate_policy_dual", group, policies,
-                                              n_subruns, subrun_first, stream_ids, engine)
+                                              n_subruns, subrun_first, stream_ids, engine,
+                                              cash_dividends)
     antithetic = bool(antithetic)
     _check_dual_sizes(n_outer, n_inner, antithetic)
     n_outer, n_inner = int(n_outer), int(n_inner)
     for c in group:
-        _check_dual_contract(c)
+        _check_dual_contract(c, cash_dividends)
     if engine == "hip":
         capi.require_device()
         P, F, S = _stack(group, ids)
         T = np.stack([pol.table() for pol in policies])
         stats, gap, cont = capi.mc_policy_dual_batch(
             P, F, S, T, G, n_outer, n_inner, antithetic, seed=seed, subrun_first=first,
-            want_gap=want_gap, want_cont=want_cont)
+            want_gap=want_gap, want_cont=want_cont, div=_div_rows(group))
     else:
         stats = np.empty((B, capi.DUAL_NSTAT))
         gap = np.empty((B, G * n_outer))
@@ -1564,7 +1651,7 @@ def simulate_policy_dual(group: Sequence[LsmContract], policies: Sequence[Exerci
             for lo in range(0, G, step):
                 hi = min(G, lo + step)
                 r = host_policy_dual_subruns(c, pol, range(first + lo, first + hi), n_outer,
-                                             n_inner, antithetic, seed, ids[b])
+                                             n_inner, antithetic, seed, ids[b], cash_dividends)
                 gap[b, lo * n_outer:hi * n_outer] = r["gaps"].reshape(-1)
                 if want_cont:
                     cont[b, lo * n_outer:hi * n_outer] = r["cont"].reshape(-1, n_steps)
@@ -1605,7 +1692,9 @@ def _policy_result(c: LsmContract, G: int, st: Optional[np.ndarray]) -> dict:
     }
 
 
-def _policy_batches(contracts, policies, cfg: LsmConfig, subrun_range, stream_ids):
+def _policy_batches(contracts, policies, cfg: LsmConfig, subrun_range, stream_ids,
+                    cash_dividends: str = "refuse"):
+    _check_cash_dividends(cash_dividends)
     plans = list(contracts)
     if any(not isinstance(c, LsmContract) for c in plans):
         raise TypeError("the table policy takes LsmContract objects (a policy is made for one)")
@@ -1614,7 +1703,7 @@ def _policy_batches(contracts, policies, cfg: LsmConfig, subrun_range, stream_id
         raise ValueError("one policy per contract")
     for c, pol in zip(plans, policies):
         if c.fixed_price is None:
-            _check_policy(c, pol)
+            _check_policy(c, pol, cash_dividends)
     lo, hi = 0, int(cfg.n_subruns)
     if hi < 1:
         raise ValueError("cfg.n_subruns must be positive.")
@@ -1626,32 +1715,36 @@ def _policy_batches(contracts, policies, cfg: LsmConfig, subrun_range, stream_id
     ids = list(range(len(plans))) if stream_ids is None else [int(s) for s in stream_ids]
     if len(ids) != len(plans):
         raise ValueError("one stream id per contract")
-    by_steps: Dict[int, List[int]] = {}
+    by_steps: Dict[tuple, List[int]] = {}
     for k, c in enumerate(plans):
         if c.fixed_price is None:
-            by_steps.setdefault(c.n_steps, []).append(k)
+            by_steps.setdefault((c.n_steps, c.has_dividends), []).append(k)
     return plans, policies, lo, hi, ids, by_steps
 
 
 def mc_policy_batch(contracts: Sequence[LsmContract], policies: Sequence[ExercisePolicy],
                     cfg: LsmConfig = LsmConfig(), *, engine: str = "hip",
                     stream_ids: Optional[Sequence[int]] = None,
-                    subrun_range: Optional[range] = None) -> List[dict]:
+                    subrun_range: Optional[range] = None,
+                    cash_dividends: str = "refuse") -> List[dict]:
     """The lower bound of many contracts under given policies, one launch per
-    distinct step count; arguments as mc_american_batch.  A `fixed_price`
+    distinct (step count, has dividends); arguments as mc_american_batch
+    (contracts that carry dividends need cash_dividends="path").  A `fixed_price`
     contract is answered without a launch (its policy is not read).  Results,
     in input order: price, stderr, ci_95, n_paths, n_subruns, steps,
     min_margin (the smallest distance of a decision's log-spot to a finite
     threshold), exercised (paths the rule stopped), barrier_type, sum_mean and
     sum_mean2 (merge_policy_stats)."""
     plans, policies, lo, hi, ids, by_steps = _policy_batches(contracts, policies, cfg,
-                                                             subrun_range, stream_ids)
+                                                             subrun_range, stream_ids,
+                                                             cash_dividends)
     out: List[Optional[dict]] = [None if c.fixed_price is None else _policy_result(c, hi - lo, None)
                                  for c in plans]
     for members in by_steps.values():
         r = simulate_policy([plans[k] for k in members], [policies[k] for k in members], hi - lo,
                             cfg.antithetic, engine=engine, seed=cfg.seed,
-                            stream_ids=[ids[k] for k in members], subrun_first=lo)
+                            stream_ids=[ids[k] for k in members], subrun_first=lo,
+                            cash_dividends=cash_dividends)
         for row, k in enumerate(members):
             out[k] = _policy_result(plans[k], hi - lo, r["stats"][row])
     return out  # type: ignore[return-value]
@@ -1659,11 +1752,12 @@ def mc_policy_batch(contracts: Sequence[LsmContract], policies: Sequence[Exercis
 
 def price_policy_mc(contract: LsmContract, policy: ExercisePolicy, *, n_subruns: int = 32,
                     antithetic: bool = True, seed: int = 42, stream_id: int = 0,
-                    engine: str = "hip") -> Dict[str, object]:
+                    engine: str = "hip", cash_dividends: str = "refuse") -> Dict[str, object]:
     """The lower bound of one contract under `policy`: mc_policy_batch's dict
     without the merging sums."""
     cfg = LsmConfig(n_subruns=int(n_subruns), antithetic=bool(antithetic), seed=int(seed))
-    res = mc_policy_batch([contract], [policy], cfg, engine=engine, stream_ids=[stream_id])[0]
+    res = mc_policy_batch([contract], [policy], cfg, engine=engine, stream_ids=[stream_id],
+                          cash_dividends=cash_dividends)[0]
     res.pop("sum_mean")
     res.pop("sum_mean2")
     return res
@@ -1672,16 +1766,19 @@ def price_policy_mc(contract: LsmContract, policy: ExercisePolicy, *, n_subruns:
 def mc_policy_bounds_batch(contracts: Sequence[LsmContract], policies: Sequence[ExercisePolicy],
                            cfg: LsmConfig = LsmConfig(), dual: DualConfig = DualConfig(), *,
                            engine: str = "hip", stream_ids: Optional[Sequence[int]] = None,
-                           subrun_range: Optional[range] = None) -> List[dict]:
+                           subrun_range: Optional[range] = None,
+                           cash_dividends: str = "refuse") -> List[dict]:
     """Lower and upper bound of many contracts under given policies: per
-    distinct step count one lower-bound launch and one dual launch.  Results:
+    distinct (step count, has dividends) one lower-bound launch and one dual
+    launch; contracts that carry dividends need cash_dividends="path".  Results:
     mc_policy_batch's dict plus what mc_american_bounds_batch adds (gap,
     gap_stderr, upper, upper_stderr, n_outer, n_inner, sum_gap, sum_gap2,
     dual_min_margin, inner_paths); `brackets` takes them as they are."""
     plans, policies, lo, hi, ids, by_steps = _policy_batches(contracts, policies, cfg,
-                                                             subrun_range, stream_ids)
+                                                             subrun_range, stream_ids,
+                                                             cash_dividends)
     for c in plans:
-        _check_dual_contract(c)
+        _check_dual_contract(c, cash_dividends)
     _check_dual_sizes(dual.n_outer, dual.n_inner, bool(cfg.antithetic))
     out: List[Optional[dict]] = [
         None if c.fixed_price is None
@@ -1689,7 +1786,7 @@ def mc_policy_bounds_batch(contracts: Sequence[LsmContract], policies: Sequence[
     for members in by_steps.values():
         group, pols = [plans[k] for k in members], [policies[k] for k in members]
         kw = dict(engine=engine, seed=cfg.seed, stream_ids=[ids[k] for k in members],
-                  subrun_first=lo)
+                  subrun_first=lo, cash_dividends=cash_dividends)
         r = simulate_policy(group, pols, hi - lo, cfg.antithetic, **kw)
         d = simulate_policy_dual(group, pols, hi - lo, dual.n_outer, dual.n_inner,
                                  cfg.antithetic, **kw)
@@ -1701,10 +1798,10 @@ def mc_policy_bounds_batch(contracts: Sequence[LsmContract], policies: Sequence[
 
 def price_policy_mc_bounds(contract: LsmContract, policy: ExercisePolicy, *, n_subruns: int = 32,
                            antithetic: bool = True, seed: int = 42, stream_id: int = 0,
-                           n_outer: int = 8, n_inner: int = 2048,
-                           engine: str = "hip") -> Dict[str, object]:
+                           n_outer: int = 8, n_inner: int = 2048, engine: str = "hip",
+                           cash_dividends: str = "refuse") -> Dict[str, object]:
     """Lower and upper bound of one contract under `policy`."""
     cfg = LsmConfig(n_subruns=int(n_subruns), antithetic=bool(antithetic), seed=int(seed))
     return mc_policy_bounds_batch([contract], [policy], cfg,
                                   DualConfig(int(n_outer), int(n_inner)), engine=engine,
-                                  stream_ids=[stream_id])[0]
+                                  stream_ids=[stream_id], cash_dividends=cash_dividends)[0]

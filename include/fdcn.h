@@ -56,7 +56,10 @@ extern "C" {
  * in fdcn_diag.h), and the least-squares Monte Carlo with cash dividends on
  * the path (fdcn_mc_lsm_div_batch, fdcn_mc_lsm_div_batch_dev), and the dual
  * upper bound of the least-squares Monte Carlo (fdcn_mc_lsm_dual_batch,
- * fdcn_mc_lsm_dual_batch_dev, fdcn_mc_lsm_dual_plan).
+ * fdcn_mc_lsm_dual_batch_dev, fdcn_mc_lsm_dual_plan), and the dual and
+ * table-policy bounds with cash dividends (fdcn_mc_lsm_dual_div_batch,
+ * fdcn_mc_policy_div_batch, fdcn_mc_policy_dual_div_batch and their _dev
+ * forms).
  * 7: the BGK barrier pricer's Monte Carlo entry points (fdcn_mc_bgk_batch,
  * fdcn_mc_bgk_batch_dev, fdcn_mc_bgk_plan) were added after 6.
  * 6: the Monte Carlo discrete-barrier entry points (fdcn_mc_barrier_batch,
@@ -940,7 +943,8 @@ int fdcn_mc_lsm_div_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t ant
  *   gap_out  [B][G * n_outer]           D per outer path (NULL: none)
  *   cont_out [B][G * n_outer][n_steps]  C_m, 0.0 where no inner simulation was
  *                                       run (NULL: none)
- * Cash dividends are out of scope: there is no `div` input.
+ * Cash dividends: there is no `div` input here; fdcn_mc_lsm_dual_div_batch
+ * below takes one.
  * Validation (before any device call; FDCN_EINVAL): that of fdcn_mc_lsm_batch
  * with subrun_first in the place of obs_first, and n_outer or n_inner out of
  * range, NULL coef, and, host entry only, a negative REBATE on a barrier
@@ -979,6 +983,45 @@ int fdcn_mc_lsm_dual_plan(int32_t n_steps, int32_t G, int32_t antithetic, int32_
                           int32_t n_inner, int64_t* ws_bytes_per_contract,
                           int64_t* gap_per_contract, int64_t* cont_per_contract);
 
+/* ---- The same with cash dividends on the path: the contract of
+ * fdcn_mc_lsm_dual_batch with one more input,
+ *   div [B][n_steps]   cash dividend D_m >= 0 of step m (0.0: none),
+ * the row of the fdcn_mc_lsm_div_batch launch that wrote coef.  Both walks go
+ * forward only, so they need the map g of fdcn_mc_lsm_div_batch and never its
+ * inverse.  Within step m, on the outer walk and on every inner walk, the order
+ * is:
+ *   1. the move x += DRIFT_m + DIFF_m * z_m;
+ *   2. the dividend, when D_m != 0.0: with s = exp(x),
+ *      x <- log(s - D_m) if s >= 2 D_m, else x - ln 2, each operation rounded
+ *      separately, ln 2 = 0x1.62e42fefa39efp-1;
+ *   3. the step's events on the ex-dividend spot: the MONITOR test, the fitted
+ *      rule's decision and its regressor u, the maturity payoff, and the
+ *      candidate of the step with the start state (x, knocked-in state) of its
+ *      inner simulation.
+ * A step with a dividend and no flag still pays it, on inner paths too: a path
+ * that is still alive takes the dividend before anything asks whether the step
+ * has an event.  The inner simulation of a start at step m begins with the move
+ * of step m + 1, so step m's dividend is in its start state and is not paid
+ * again.  Streams, the observation packing, the sums, the tree, stats, gap_out
+ * and cont_out are unchanged, fdcn_mc_lsm_dual_plan serves both forms, and a
+ * launch with an all-zero div gives the numbers of fdcn_mc_lsm_dual_batch bit
+ * for bit.  D >= 0 holds as before: g does not enter the argument.
+ * Validation adds (before any device call; FDCN_EINVAL): div NULL; and, host
+ * entry only, a dividend that is negative or not finite. */
+int fdcn_mc_lsm_dual_div_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                               int32_t n_outer, int32_t n_inner, const double* params,
+                               const int32_t* flags, const double* step, const double* div,
+                               const double* coef, uint64_t seed, int64_t subrun_first,
+                               double* stats, double* gap_out, double* cont_out);
+/* Device pointers, as fdcn_mc_lsm_dual_batch_dev; the contents of div are not
+ * checked here. */
+int fdcn_mc_lsm_dual_div_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                                   int32_t n_outer, int32_t n_inner, const double* params,
+                                   const int32_t* flags, const double* step, const double* div,
+                                   const double* coef, uint64_t seed, int64_t subrun_first,
+                                   double* stats, double* gap_out, double* cont_out,
+                                   double* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Monte Carlo bounds under a given exercise table (csrc/fdcn_mc_policy.hip,
  * csrc/fdcn_mc_policy.h).  The least-squares Monte Carlo fits its stopping
  * rule; here the rule is an input, for instance the exercise boundary of a
@@ -1006,7 +1049,8 @@ int fdcn_mc_lsm_dual_plan(int32_t n_steps, int32_t G, int32_t antithetic, int32_
  * MIN_MARGIN is the smallest distance |x - X_LO_m|, |x - X_HI_m| to a finite
  * entry over those decisions: no decision of a run can flip under a
  * perturbation of x smaller than it.
- * Cash dividends are out of scope: there is no `div` input.
+ * Cash dividends: there is no `div` input here; fdcn_mc_policy_div_batch and
+ * fdcn_mc_policy_dual_div_batch below take one.
  *
  * Lower bound, fdcn_mc_policy_batch.  The paths are the LSM's price set:
  * counter word 3 = 2 * stream id + 1, the observation mapping, the antithetic
@@ -1055,6 +1099,30 @@ int fdcn_mc_policy_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t anti
  * NULL.  Host only. */
 int fdcn_mc_policy_plan(int32_t n_steps, int32_t G, int32_t antithetic, int32_t* obs_per_subrun,
                         int64_t* ws_bytes_per_contract, int64_t* values_per_contract);
+/* The same with cash dividends on the path: one more input,
+ *   div [B][n_steps]   cash dividend D_m >= 0 of step m (0.0: none).
+ * Within step m the order is: the move x += DRIFT_m + DIFF_m * z_m; then the
+ * dividend, when D_m != 0.0, through the forward map of fdcn_mc_lsm_div_batch
+ * (x <- log(exp(x) - D_m) if exp(x) >= 2 D_m, else x - ln 2); then the step's
+ * events on the ex-dividend spot: the MONITOR test, the band decision in x and
+ * the maturity payoff.  A step with a dividend and no flag still pays it.  A
+ * dividend step evaluates exp and log once for the map; elsewhere the spot is
+ * read only where stated above.  With a table that never stops, PRICE, STDERR,
+ * SUM, SUM2 and values_out are those of fdcn_mc_lsm_div_batch on the contract
+ * with its EXERCISE flags cleared, bit for bit; with an all-zero div every
+ * output is that of fdcn_mc_policy_batch, bit for bit.  fdcn_mc_policy_plan
+ * serves both forms.
+ * Validation adds (before any device call; FDCN_EINVAL): div NULL; and, host
+ * entry only, a dividend that is negative or not finite. */
+int fdcn_mc_policy_div_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                             const double* params, const int32_t* flags, const double* step,
+                             const double* div, const double* policy, uint64_t seed,
+                             int64_t obs_first, double* stats, double* values_out);
+int fdcn_mc_policy_div_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                                 const double* params, const int32_t* flags, const double* step,
+                                 const double* div, const double* policy, uint64_t seed,
+                                 int64_t obs_first, double* stats, double* values_out,
+                                 double* workspace, int64_t workspace_bytes, void* stream);
 
 /* Upper bound, fdcn_mc_policy_dual_batch: the contract of
  * fdcn_mc_lsm_dual_batch with policy [B][n_steps][FDCN_POLICY_NCOL] in the
@@ -1082,6 +1150,29 @@ int fdcn_mc_policy_dual_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t
 int fdcn_mc_policy_dual_plan(int32_t n_steps, int32_t G, int32_t antithetic, int32_t n_outer,
                              int32_t n_inner, int64_t* ws_bytes_per_contract,
                              int64_t* gap_per_contract, int64_t* cont_per_contract);
+/* The same with cash dividends on the path: div [B][n_steps] as in
+ * fdcn_mc_policy_div_batch, and the order within a step of
+ * fdcn_mc_lsm_dual_div_batch on the outer walk and on every inner walk: the
+ * move, the dividend (a step without a flag pays it too), then the MONITOR
+ * test, the band decision in x, the maturity payoff and the candidate with the
+ * start state of its inner simulation, all on the ex-dividend spot.  With a
+ * table that never stops, every output is that of fdcn_mc_lsm_dual_div_batch
+ * with an all-zero coef, bit for bit; with an all-zero div, that of
+ * fdcn_mc_policy_dual_batch.  fdcn_mc_policy_dual_plan serves both forms.
+ * Validation adds: div NULL; and, host entry only, a dividend that is negative
+ * or not finite. */
+int fdcn_mc_policy_dual_div_batch(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                                  int32_t n_outer, int32_t n_inner, const double* params,
+                                  const int32_t* flags, const double* step, const double* div,
+                                  const double* policy, uint64_t seed, int64_t subrun_first,
+                                  double* stats, double* gap_out, double* cont_out);
+int fdcn_mc_policy_dual_div_batch_dev(int32_t B, int32_t n_steps, int32_t G, int32_t antithetic,
+                                      int32_t n_outer, int32_t n_inner, const double* params,
+                                      const int32_t* flags, const double* step,
+                                      const double* div, const double* policy, uint64_t seed,
+                                      int64_t subrun_first, double* stats, double* gap_out,
+                                      double* cont_out, double* workspace,
+                                      int64_t workspace_bytes, void* stream);
 
 /* ---- host-side plan helpers (no device) -------------------------------- */
 /* Uniform log grid of the pricers' _build_log_grid

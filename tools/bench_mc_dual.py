@@ -17,6 +17,12 @@ Yardstick, same process: the NumPy host engine (mc_american.host_dual_subruns,
 the same estimator on the same streams under the same policies) on the first
 `--host-contracts` contracts x `--host-subruns` sub-runs, one thread.
 
+--dividends N puts a cash dividend on N steps of every contract
+(bench_mc_lsm.py's rows: 0.4 % of the spot, spread over the life, none on the
+last step) and times the dividend instance (fdcn_mc_lsm_dual_div_batch_dev)
+under the same coefficients beside the plain launch, in the same process; the
+record carries both launch times, their ratio and both inner path-step counts.
+
 Prints one JSON line.  --dump-outputs DIR writes the stats of the last timed
 launch as DIR/mc_dual_stats.npy.  Without a GPU it fails; there is no fallback.
 """
@@ -35,10 +41,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from bench_mc_lsm import build_batch  # noqa: E402
+from bench_mc_lsm import build_batch, dividend_rows  # noqa: E402
 
 
-def device_run(plans, G: int, n_outer: int, n_inner: int, launches: int, warmup: int, seed: int):
+def device_run(plans, G: int, n_outer: int, n_inner: int, launches: int, warmup: int, seed: int,
+               div=None):
     import torch
     from finite_difference_amd import capi, mc_american
     capi.require_device()
@@ -61,6 +68,20 @@ def device_run(plans, G: int, n_outer: int, n_inner: int, launches: int, warmup:
                                dF.data_ptr(), dS.data_ptr(), coef.data_ptr(), seed, 0,
                                stats.data_ptr(), None, None, ws.data_ptr(), ws_bytes,
                                stream.cuda_stream)
+
+    def timed(fn):
+        out = []
+        for _ in range(warmup):
+            fn()
+        stream.synchronize()
+        for _ in range(launches):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(stream)
+            fn()
+            t1.record(stream)
+            t1.synchronize()
+            out.append(t0.elapsed_time(t1) * 1e-3)
+        return out
     times = []
     with torch.cuda.stream(stream):
         capi.mc_lsm_batch_dev(B, n_steps, G, True, dP.data_ptr(), dF.data_ptr(), dS.data_ptr(),
@@ -76,8 +97,22 @@ def device_run(plans, G: int, n_outer: int, n_inner: int, launches: int, warmup:
             t1.record(stream)
             t1.synchronize()
             times.append(t0.elapsed_time(t1) * 1e-3)
-    return (times, stats.cpu().numpy(), lsm_stats.cpu().numpy(), coef.cpu().numpy(),
-            torch.cuda.get_device_name(0))
+    out = (times, stats.cpu().numpy(), lsm_stats.cpu().numpy(), coef.cpu().numpy(),
+           torch.cuda.get_device_name(0))
+    if div is None:
+        return out
+    dD = torch.from_numpy(np.ascontiguousarray(div)).to(dev)
+    dstats = torch.zeros((B, capi.DUAL_NSTAT), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+
+    def launch_div():
+        capi.mc_dual_div_batch_dev(B, n_steps, G, True, n_outer, n_inner, dP.data_ptr(),
+                                   dF.data_ptr(), dS.data_ptr(), dD.data_ptr(), coef.data_ptr(),
+                                   seed, 0, dstats.data_ptr(), None, None, ws.data_ptr(),
+                                   ws_bytes, stream.cuda_stream)
+    with torch.cuda.stream(stream):
+        dtimes = timed(launch_div)
+    return out + (dtimes, dstats.cpu().numpy())
 
 
 def host_run(plans, coef, G: int, n_outer: int, n_inner: int, seed: int):
@@ -105,12 +140,15 @@ def main() -> int:
     ap.add_argument("--host-contracts", type=int, default=7)
     ap.add_argument("--host-subruns", type=int, default=1)
     ap.add_argument("--dump-outputs", default="", metavar="DIR")
+    ap.add_argument("--dividends", type=int, default=0, metavar="N",
+                    help="also time the dividend instance with N dividend steps per contract")
     args = ap.parse_args()
 
     from finite_difference_amd import capi
     plans = build_batch(args.contracts, args.steps)
-    times, stats, lsm_stats, coef, name = device_run(plans, args.subruns, args.outer, args.inner,
-                                                     args.launches, args.warmup, args.seed)
+    rows = dividend_rows(plans, args.dividends) if args.dividends else None
+    times, stats, lsm_stats, coef, name, *with_div = device_run(
+        plans, args.subruns, args.outer, args.inner, args.launches, args.warmup, args.seed, rows)
     med = statistics.median(times)
     steps = float(stats[:, capi.DUAL_O_INNER_STEPS].sum())
     paths = float(stats[:, capi.DUAL_O_INNER_PATHS].sum())
@@ -134,6 +172,19 @@ def main() -> int:
         "gap_range": [float(gap.min()), float(gap.max())],
         "median_gap_over_lower_bound": float(np.median(gap / np.maximum(low, 1e-300))),
     }
+    if args.dividends:
+        dt, dstats = with_div
+        dmed = statistics.median(dt)
+        dsteps = float(dstats[:, capi.DUAL_O_INNER_STEPS].sum())
+        line["dividends"] = {
+            "steps_with_a_dividend": args.dividends,
+            "launch_seconds": {"median": dmed, "min": min(dt), "max": max(dt)},
+            "plain_launch_seconds_median": med,
+            "ratio_to_plain": dmed / med,
+            "inner_path_steps_per_launch": dsteps,
+            "inner_path_steps_per_s": dsteps / dmed,
+            "gap_range": [float(dstats[:, 0].min()), float(dstats[:, 0].max())],
+        }
     if args.dump_outputs:
         os.makedirs(args.dump_outputs, exist_ok=True)
         np.save(os.path.join(args.dump_outputs, "mc_dual_stats.npy"), stats)

@@ -22,6 +22,13 @@ on the first `--host-contracts` contracts x `--host-subruns` sub-runs.
 fdcn_mc_lsm_dual_batch_dev (under the coefficients the LSM launch has just
 fitted), each in inner path-steps as the kernels count them.
 
+--dividends N puts a cash dividend on N steps of every contract
+(bench_mc_lsm.py's rows: 0.4 % of the spot, spread over the life, none on the
+last step) and times fdcn_mc_policy_div_batch_dev -- with --dual also
+fdcn_mc_policy_dual_div_batch_dev and fdcn_mc_lsm_dual_div_batch_dev, under the
+same table and coefficients -- beside the plain launches, in the same process;
+the record carries the launch times and their ratios to the plain ones.
+
 Prints one JSON line.  --dump-outputs DIR writes the stats of the last timed
 launches as DIR/mc_policy_stats.npy (and mc_policy_dual_stats.npy).  Without a
 GPU it fails; there is no fallback.
@@ -41,7 +48,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from bench_mc_lsm import build_batch  # noqa: E402
+from bench_mc_lsm import build_batch, dividend_rows  # noqa: E402
 
 
 def threshold_policies(plans):
@@ -73,7 +80,7 @@ def _timed(stream, launch, launches: int, warmup: int):
     return times
 
 
-def device_run(plans, pols, G: int, launches: int, warmup: int, seed: int, dual):
+def device_run(plans, pols, G: int, launches: int, warmup: int, seed: int, dual, div=None):
     import torch
     from finite_difference_amd import capi, mc_american
     capi.require_device()
@@ -122,6 +129,31 @@ def device_run(plans, pols, G: int, launches: int, warmup: int, seed: int, dual)
         out["policy_dual"] = _timed(stream, policy_dual, launches, warmup)
         out["fitted_dual"] = _timed(stream, fitted_dual, launches, warmup)
         out["dual_stats"], out["fitted_dual_stats"] = dstats.cpu().numpy(), fstats.cpu().numpy()
+    if div is not None:  # after every plain launch, so that those are the runs without the flag
+        dD = torch.from_numpy(np.ascontiguousarray(div)).to(dev)
+        vstats = torch.zeros((B, capi.POLICY_NSTAT), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+
+        def policy_div():
+            capi.mc_policy_div_batch_dev(*head, dD.data_ptr(), dT.data_ptr(), seed, 0,
+                                         vstats.data_ptr(), None, *tail)
+        out["policy_div"] = _timed(stream, policy_div, launches, warmup)
+        out["div_stats"] = vstats.cpu().numpy()
+        if dual:
+            vd = torch.zeros((B, capi.DUAL_NSTAT), dtype=torch.float64, device=dev)
+            vf = torch.zeros((B, capi.DUAL_NSTAT), dtype=torch.float64, device=dev)
+            torch.cuda.synchronize()
+
+            def policy_dual_div():
+                capi.mc_policy_dual_div_batch_dev(*dhead, dD.data_ptr(), dT.data_ptr(), seed, 0,
+                                                  vd.data_ptr(), None, None, *tail)
+
+            def fitted_dual_div():
+                capi.mc_dual_div_batch_dev(*dhead, dD.data_ptr(), coef.data_ptr(), seed, 0,
+                                           vf.data_ptr(), None, None, *tail)
+            out["policy_dual_div"] = _timed(stream, policy_dual_div, launches, warmup)
+            out["fitted_dual_div"] = _timed(stream, fitted_dual_div, launches, warmup)
+            out["dual_div_stats"], out["fitted_dual_div_stats"] = vd.cpu().numpy(), vf.cpu().numpy()
     return out
 
 
@@ -157,13 +189,16 @@ def main() -> int:
     ap.add_argument("--outer", type=int, default=8)
     ap.add_argument("--inner", type=int, default=2048)
     ap.add_argument("--dump-outputs", default="", metavar="DIR")
+    ap.add_argument("--dividends", type=int, default=0, metavar="N",
+                    help="also time the dividend instances with N dividend steps per contract")
     args = ap.parse_args()
 
     from finite_difference_amd import capi
     plans = build_batch(args.contracts, args.steps)
     pols = threshold_policies(plans)
     r = device_run(plans, pols, args.subruns, args.launches, args.warmup, args.seed,
-                   (args.outer, args.inner) if args.dual else None)
+                   (args.outer, args.inner) if args.dual else None,
+                   dividend_rows(plans, args.dividends) if args.dividends else None)
     med, lsm_med = statistics.median(r["policy"]), statistics.median(r["lsm"])
     paths = args.contracts * args.subruns * capi.LSM_SUBRUN
     rate = paths * args.steps / med
@@ -203,6 +238,26 @@ def main() -> int:
                        "inner_path_steps_per_launch": fs, "inner_path_steps_per_s": fs / fm,
                        "gap_range": [float(f[:, 0].min()), float(f[:, 0].max())]},
         }
+    if args.dividends:
+        vm = statistics.median(r["policy_div"])
+        line["dividends"] = {
+            "steps_with_a_dividend": args.dividends,
+            "launch_seconds": _secs(r["policy_div"], args.launches, args.warmup),
+            "plain_launch_seconds_median": med,
+            "ratio_to_plain": vm / med,
+            "price_range": [float(r["div_stats"][:, 0].min()), float(r["div_stats"][:, 0].max())],
+        }
+        if args.dual:
+            for key, plain in (("policy_dual", dm), ("fitted_dual", fm)):
+                t = r[key + "_div"]
+                st = r[("dual_div_stats" if key == "policy_dual" else "fitted_dual_div_stats")]
+                steps = float(st[:, capi.DUAL_O_INNER_STEPS].sum())
+                line["dividends"][key] = {
+                    "launch_seconds": _secs(t, args.launches, args.warmup),
+                    "plain_launch_seconds_median": plain,
+                    "ratio_to_plain": statistics.median(t) / plain,
+                    "inner_path_steps_per_launch": steps,
+                    "inner_path_steps_per_s": steps / statistics.median(t)}
     if args.dump_outputs:
         os.makedirs(args.dump_outputs, exist_ok=True)
         np.save(os.path.join(args.dump_outputs, "mc_policy_stats.npy"), stats)
